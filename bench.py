@@ -5,21 +5,26 @@ A "step" is one pass of the hot path (fused AD + 11x11 box SAD + WTA, bit-exact 
 reference's getDisp / kernalFindCorr) over one batch of synthetic rectified 1920x1080 pairs
 that are already resident in HBM when the timed region starts.
 
-    python bench.py                      # N=1, defaults
+    python bench.py                      # N=1, defaults: the headline only
+    python bench.py --full               # + CPU baselines, roofline, latency, cfg5, per-config table
+    python bench.py --dump-outputs DIR   # + the last timed step's disparity maps as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times exactly --steps steps and prints the result line.  Everything
+else the benchmark measures or checks runs only with --full.
 
 Multi-GPU: one process per GPU.  The path partitions by frame (independent pairs), so ranks
-shard frames with no data-path collective ("scaling": "weak").  The two single-frame modes of
+shard frames with no data-path collective ("scaling": "weak").  With --full, the two single-frame modes of
 SURVEY §8e are measured in the same run for N > 1: "dslice" (cfg4: each rank owns a disparity
 slice of the SAME 1080p d_max=256 frame; packed-key MIN reduce-scatter + uint8 all-gather over
 RCCL, and the plain MIN all-reduce beside it) and "rowband" (each rank owns a band of rows plus an
-r-row halo, all-gather of the uint8 bands).  "cfg5_guided_lr" (every N) is BASELINE configs[4] as
+r-row halo, all-gather of the uint8 bands).  "cfg5_guided_lr" (--full, every N) is BASELINE configs[4] as
 written: 4K pairs, d_max=192, guided filter + LR check, frames batched over all ranks.
 
 Rank 0 prints ONE JSON line.  Timing: barrier + synchronize on both sides of exactly K steps,
-max over ranks.  The dominant kernel's duration is measured live with HIP events on the stream
-the kernels are launched on (torch's current stream, passed through the C ABI).
+max over ranks.  With --full the dominant kernel's duration is measured live with HIP events on the
+stream the kernels are launched on (torch's current stream, passed through the C ABI).
 """
 from __future__ import annotations
 
@@ -59,12 +64,19 @@ def parse():
                     help="frames per step per GPU (128 x 1080p pairs = 531 MB resident; amortises the launch tail: "
                          "18.2k maps/s vs 17.9k at 32 and 18.1k at 64, profiles/microbench/r02_headline_batch.txt)")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the per-config / LR / guided table")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement")
-    ap.add_argument("--no-cfg5", action="store_true", help="skip the 4K guided+LR frame-parallel block")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: CPU baselines, per-step kernel events and the VALU roofline, batch-1 "
+                         "latency, the N > 1 single-frame splits with their parity checks, cfg5 and the per-config table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the disparity maps of the last step as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of the pixels when the maps exceed the size budget)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the per-config / LR / guided table")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latency measurement")
+    ap.add_argument("--no-cfg5", action="store_true", help="with --full: skip the 4K guided+LR frame-parallel block")
     ap.add_argument("--profile", action="store_true",
-                    help="only the timed steps (what rocprof summaries under profiles/ are taken from)")
+                    help="--full without the CPU baselines, table, latency and cfg5: the timed steps with their kernel "
+                         "events and roofline (what rocprof summaries under profiles/ are taken from)")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_box_r5_1080p.json"))
     ap.add_argument("--valu-json", default=os.path.join(ROOT, "profiles", "valu_counts.json"))
     return ap.parse_args()
@@ -152,6 +164,38 @@ def valu_roofline(counts, key, workload, launch_ms, kernel, extra=None, symbol=N
     if extra:
         res.update(extra)
     return res
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # all files of one --dump-outputs run together
+DUMP_SAMPLE_SEED = 20240531
+
+
+def synth_batch(sm, seed0, n, W, H, D):
+    """n synthetic pairs, seeds seed0 .. seed0 + n - 1, stacked to two [n, H, W] uint8 arrays; generated on
+    the host cores this job may use (numpy releases the GIL), identical to calling synth_pair in a loop."""
+    from concurrent.futures import ThreadPoolExecutor
+    workers = max(1, min(16, n, len(os.sched_getaffinity(0))))
+    with ThreadPoolExecutor(workers) as pool:
+        pairs = list(pool.map(lambda i: sm.synth_pair(seed0 + i, W, H, D), range(n)))
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+
+
+def dump_outputs(torch, directory, out, rank, world):
+    """The maps the last timed step left in `out` ([B, H, W] uint8, what match_device hands its caller), as
+    float32 .npy.  Each rank writes its own frames; the ranks share DUMP_BUDGET_BYTES.  A batch over the budget is
+    written as the values at a fixed set of flat pixel indices (seeded, the same in every run and every build)."""
+    os.makedirs(directory, exist_ok=True)
+    name = "disparity" if world == 1 else f"disparity_rank{rank}"
+    budget = DUMP_BUDGET_BYTES // world // 4 - 64        # float32 elements; 64 elements spare for the .npy header
+    flat = out.reshape(-1)
+    if flat.numel() > budget:
+        # half the budget: enough pixels to see any frame or tile go wrong, and a small copy and file
+        idx = np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), size=budget // 2, dtype=np.int64)
+        flat = flat[torch.from_numpy(idx).to(out.device)]
+        arr = flat.to(torch.float32).cpu().numpy()
+    else:
+        arr = flat.to(torch.float32).cpu().numpy().reshape(tuple(out.shape))
+    np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def cpu_baseline(W, H, D, r, seed):
@@ -576,8 +620,11 @@ def run_split_extras(sm, torch, dist, m, Lc, Rc, W, H, D, r, rank, world, dev, s
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.profile:
-        args.no_cpu_baseline = args.no_variants = args.no_latency = args.no_cfg5 = True
+        args.full = args.no_cpu_baseline = args.no_variants = args.no_latency = args.no_cfg5 = True
+    full = args.full
     import torch
     import torch.distributed as dist
 
@@ -586,7 +633,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # CPU baselines first, before this process initialises the GPU (the all-cores leg forks)
     cpu = cpu_all = None
-    if not args.no_cpu_baseline and world == 1:
+    if full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.width, args.height, args.num_disp, args.radius, args.seed)
         cpu_all = cpu_baseline_all_cores(args.width, args.height, args.num_disp, args.radius, args.seed)
     distributed = world > 1
@@ -608,13 +655,10 @@ def main():
     m = sm.BlockMatcher(dev_index, W, H, 256)
 
     # synthetic frames for this rank: seeds seed + global frame index (disjoint per rank)
-    Ls, Rs = [], []
-    for i in range(B):
-        L, R = sm.synth_pair(args.seed + rank * B + i, W, H, D)
-        Ls.append(L)
-        Rs.append(R)
-    Lt = torch.from_numpy(np.stack(Ls)).to(dev)
-    Rt = torch.from_numpy(np.stack(Rs)).to(dev)
+    Ls, Rs = synth_batch(sm, args.seed + rank * B, B, W, H, D)
+    Lt = torch.from_numpy(Ls).to(dev)
+    Rt = torch.from_numpy(Rs).to(dev)
+    del Ls, Rs
     out = torch.empty_like(Lt)
     stream = torch.cuda.current_stream(dev)
 
@@ -625,21 +669,26 @@ def main():
         step()
     torch.cuda.synchronize(dev)
 
-    # per-launch kernel timing on the launch stream (one launch per step)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full: per-launch kernel timing on the launch stream (one launch per step)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(args.steps if full else 0)]
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    for k in range(args.steps):
-        ev[k][0].record(stream)
-        step()
-        ev[k][1].record(stream)
+    if full:
+        for k in range(args.steps):
+            ev[k][0].record(stream)
+            step()
+            ev[k][1].record(stream)
+    else:
+        for k in range(args.steps):
+            step()
     torch.cuda.synchronize(dev)
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else None
 
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -650,9 +699,12 @@ def main():
     value = frames_total / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps
 
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, out, rank, world)
+
     # ---- single-frame latency (batch 1, device resident) ----
     lat = None
-    if rank == 0 and not args.no_latency:
+    if full and rank == 0 and not args.no_latency:
         o1 = torch.empty_like(Lt[0])
         for _ in range(5):
             m.match_device(Lt[0], Rt[0], r, D, out_t=o1, stream=stream)
@@ -666,7 +718,7 @@ def main():
 
     # ---- d-slice sharding of one frame (N > 1): cfg4, 1080p d_max=256, MIN reduction of the slice keys ----
     dslice = rowband = inventory = None
-    if distributed:
+    if full and distributed:
         try:
             inventory = rank_inventory(torch, dist, dev, backend)
         except Exception as e:  # report, never hide
@@ -683,7 +735,7 @@ def main():
     # ---- cfg5 as BASELINE configs[4] writes it: 4K pairs, d_max=192, guided + LR, frames batched
     #      over every rank (frame-parallel, no collective), whole-job maps/s with the max-over-ranks clock ----
     cfg5 = None
-    if not args.no_cfg5:
+    if full and not args.no_cfg5:
         W5, H5, D5, B5 = 3840, 2160, 192, 8
         m5 = sm.BlockMatcher(dev_index, W5, H5, 256)
         try:
@@ -759,30 +811,32 @@ def main():
 
     # ---- BASELINE configs, LR and guided variants on rank 0 ----
     variants = None
-    if rank == 0 and not args.no_variants:
+    if full and rank == 0 and not args.no_variants:
         variants = run_variants(sm, torch, dev, stream, args.seed)
 
     if rank == 0:
         bpm = algorithmic_bytes_per_map(W, H, D)
-        eq_hbm = bpm * B / (kern_ms * 1e-3) / 1e9
-        traffic = None
-        try:
-            with open(args.pmc_json) as f:
-                pm = json.load(f)
-            if pm.get("workload") == [W, H, D, r, B]:
-                traffic = pm.get("hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            pass
-        counts = load_counts(args.valu_json)
-        roof = valu_roofline(counts, f"box_r5_1080p_d128_b{B}", [W, H, D, r, B], kern_ms, f"box_match_kernel<{r}>", {
-            "traffic": traffic,
-            "traffic_frac_of_hbm_peak": round(traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-            "equivalent_hbm_frac": round(eq_hbm / HBM_PEAK_GBS, 4),
-            "algorithmic_bytes_per_launch": bpm * B,
-            "note": "bound = VALU issue (the fused kernel reads the pair and writes the map: measured HBM traffic is "
-                    "the compulsory 3P bytes, traffic_frac_of_hbm_peak); equivalent_hbm_frac = P*(2D+3) bytes per "
-                    "map (SURVEY §8d, the reference's AD-volume data flow, never materialised here) / launch time / "
-                    "8 TB/s: a speed figure, not a roofline fraction (DESIGN.md §8)"})
+        roof = counts = None
+        if full:
+            eq_hbm = bpm * B / (kern_ms * 1e-3) / 1e9
+            traffic = None
+            try:
+                with open(args.pmc_json) as f:
+                    pm = json.load(f)
+                if pm.get("workload") == [W, H, D, r, B]:
+                    traffic = pm.get("hbm_bytes_per_launch")
+            except (OSError, ValueError):
+                pass
+            counts = load_counts(args.valu_json)
+            roof = valu_roofline(counts, f"box_r5_1080p_d128_b{B}", [W, H, D, r, B], kern_ms, f"box_match_kernel<{r}>", {
+                "traffic": traffic,
+                "traffic_frac_of_hbm_peak": round(traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                "equivalent_hbm_frac": round(eq_hbm / HBM_PEAK_GBS, 4),
+                "algorithmic_bytes_per_launch": bpm * B,
+                "note": "bound = VALU issue (the fused kernel reads the pair and writes the map: measured HBM traffic is "
+                        "the compulsory 3P bytes, traffic_frac_of_hbm_peak); equivalent_hbm_frac = P*(2D+3) bytes per "
+                        "map (SURVEY §8d, the reference's AD-volume data flow, never materialised here) / launch time / "
+                        "8 TB/s: a speed figure, not a roofline fraction (DESIGN.md §8)"})
         res = {
             "metric": "disparity-maps/sec + ms/frame, 1080p d_max=128",
             "value": round(value, 2),

@@ -1,0 +1,73 @@
+"""bench.py's command line: a plain run times exactly --steps steps and does nothing beside its headline,
+--dump-outputs writes what the last timed step computed, and the pieces both rely on (threaded frame
+generation, the seeded sample of a batch over the size budget) are deterministic."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def test_synth_batch_equals_the_serial_loop():
+    import bench
+    import gpu_stereo_matching_amd as sm
+    Ls, Rs = bench.synth_batch(sm, 77, 5, 96, 40, 32)
+    assert Ls.shape == Rs.shape == (5, 40, 96) and Ls.dtype == np.uint8
+    for i in range(5):
+        L, R = sm.synth_pair(77 + i, 96, 40, 32)
+        assert np.array_equal(Ls[i], L) and np.array_equal(Rs[i], R)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    import torch
+    import bench
+    out = torch.from_numpy(np.random.default_rng(5).integers(0, 256, size=(3, 37, 53), dtype=np.uint8))
+    # under the budget: the maps themselves, float32, in the batch's shape
+    bench.dump_outputs(torch, str(tmp_path / "whole"), out, 0, 1)
+    a = np.load(tmp_path / "whole" / "disparity.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, out.numpy().astype(np.float32))
+    # over the budget: the same seeded pixels in every run, every one a pixel of the batch, files within budget
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8192)
+    for d in ("s1", "s2"):
+        for rank in (0, 1):
+            bench.dump_outputs(torch, str(tmp_path / d), out, rank, 2)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["disparity_rank0.npy", "disparity_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 8192
+    s1, s2 = np.load(tmp_path / "s1" / files[0]), np.load(tmp_path / "s2" / files[0])
+    assert s1.dtype == np.float32 and s1.ndim == 1 and 0 < s1.size < out.numel()
+    assert np.array_equal(s1, s2)
+    idx = np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, out.numel(), size=s1.size, dtype=np.int64)
+    assert np.array_equal(s1, out.numpy().reshape(-1)[idx].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_map(tmp_path, oracle):
+    import gpu_stereo_matching_amd as sm
+    W, H, D, r, B, seed = 200, 72, 32, 2, 3, 99
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--width", str(W), "--height", str(H), "--num-disp", str(D), "--radius", str(r), "--batch", str(B),
+           "--seed", str(seed), "--dump-outputs", str(tmp_path / "dump")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
+    assert res["unit"] == "disparity-maps/s" and res["higher_is_better"] is True and res["dtype"] == "u8"
+    assert res["ms_per_step"] > 0
+    assert res["value"] == pytest.approx(B * 1000.0 / res["ms_per_step"], rel=1e-3)
+    # nothing beside the headline in a plain run
+    for key in ("variants", "cfg5_guided_lr", "cfg3_guided", "staged_hbm_roofline", "dslice", "rowband"):
+        assert key not in res
+    assert res["roofline"] is None and res["cpu_baseline"] is None and res["latency_ms_batch1"] is None
+    got = np.load(tmp_path / "dump" / "disparity.npy")
+    assert got.dtype == np.float32 and got.shape == (B, H, W)
+    for i in range(B):
+        L, R = sm.synth_pair(seed + i, W, H, D)
+        assert np.array_equal(got[i], oracle.box_disp(L, R, r, D).astype(np.float32)), f"frame {i}"

@@ -34,7 +34,7 @@ if has staged; then
   SM_TAG=_${TAG} timeout -k 10 300 python tools/staged_roofline.py > ${O}_staged.txt 2>&1 || { tail -5 ${O}_staged.txt; exit 4; }
 fi
 if has bench; then
-  timeout -k 10 500 python bench.py $VJ > ${O}_bench.json 2> ${O}_bench.err || { tail -5 ${O}_bench.err; exit 5; }
+  timeout -k 10 500 python bench.py --full $VJ > ${O}_bench.json 2> ${O}_bench.err || { tail -5 ${O}_bench.err; exit 5; }
   python -c "
 import json; d=json.load(open('${O}_bench.json'))
 print(d['value'], d['ms_per_step'], d['roofline']['frac'])

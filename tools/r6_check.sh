@@ -13,7 +13,7 @@ timeout -k 10 900 python -u -m pytest -x -q -m gpu --timeout 300 --timeout-metho
   > gpurun_out/${TAG}_tests.txt 2>&1 || { tail -30 gpurun_out/${TAG}_tests.txt; exit 1; }
 tail -3 gpurun_out/${TAG}_tests.txt
 SM_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --no-variants \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --full --no-variants \
   > gpurun_out/${TAG}_n2_gloo.json 2> gpurun_out/${TAG}_n2_gloo.err || { tail -20 gpurun_out/${TAG}_n2_gloo.err; exit 2; }
 python - <<PY
 import json

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest -x -q -m gpu --timeout 300 --timeout-metho
   tests/test_gpu_dslice_lr.py -k "fuzz" > gpurun_out/${TAG}_tests.txt 2>&1 || { tail -30 gpurun_out/${TAG}_tests.txt; exit 1; }
 tail -2 gpurun_out/${TAG}_tests.txt
 SM_DIST_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-  --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 4 --steps 8 --warmup 2 --no-variants --batch 32 \
+  --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 4 --steps 8 --warmup 2 --full --no-variants --batch 32 \
   > gpurun_out/${TAG}_n4_gloo.json 2> gpurun_out/${TAG}_n4_gloo.err || { tail -20 gpurun_out/${TAG}_n4_gloo.err; exit 2; }
 python - <<PY
 import json
