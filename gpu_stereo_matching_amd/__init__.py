@@ -22,13 +22,14 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID  # noqa: F401
+from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID, SM_AGG_SGM  # noqa: F401
 from .synth import synth_pair  # noqa: F401
 from .gray import bgr_to_gray  # noqa: F401
 
 __all__ = [
     "BlockMatcher", "BlockMatcherGroup", "blockMatching_gpu", "block_matching_gpu", "SMError", "synth_pair", "bgr_to_gray",
-    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
+    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
+    "sgm_penalties", "sgm_workspace_bytes",
 ]
 
 DEFAULT_GUIDED_EPS = 1e-4 * 255.0 * 255.0
@@ -46,13 +47,30 @@ def _as_u8_image(a, name: str) -> np.ndarray:
 
 
 def _flags(agg: str, lr_check: bool, median: bool = False) -> int:
-    """agg: 'box' (fused), 'box-staged' (through the AD / SAD volumes in HBM), 'guided', or 'device-cu'
-    (Device.cu's literal output with its fixed launch geometry: SM_DEVICE_CU_GRID, box only)."""
-    if agg not in ("box", "guided", "box-staged", "device-cu"):
-        raise ValueError("agg must be 'box', 'box-staged', 'guided' or 'device-cu'")
+    """agg: 'box' (fused), 'box-staged' (through the AD / SAD volumes in HBM), 'guided', 'sgm' (four-path
+    semi-global matching on the box SAD volume, radius <= 7), or 'device-cu' (Device.cu's literal output with
+    its fixed launch geometry: SM_DEVICE_CU_GRID, box only)."""
+    if agg not in ("box", "guided", "box-staged", "device-cu", "sgm"):
+        raise ValueError("agg must be 'box', 'box-staged', 'guided', 'sgm' or 'device-cu'")
     f = {"box": SM_AGG_BOX, "guided": SM_AGG_GUIDED, "box-staged": SM_AGG_BOX | SM_STAGED,
-         "device-cu": SM_DEVICE_CU_GRID}[agg]
+         "device-cu": SM_DEVICE_CU_GRID, "sgm": SM_AGG_SGM}[agg]
     return f | (SM_LR_CHECK if lr_check else 0) | (SM_MEDIAN if median else 0)
+
+
+def sgm_penalties(radius: int, p1: int = 0, p2: int = 0, width: int = 1) -> Tuple[int, int]:
+    """The (P1, P2) an 'sgm' match at `radius` uses for the parameter values p1, p2 (0 = auto: 8 win^2 and
+    32 win^2), through the library's own argument check (sm_sgm_check, host-only); raises SMError where
+    the match would (P1 > P2, 255 win^2 + P2 > 65535, radius > 7, width > 4096)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _capi.check(_capi.load().sm_sgm_check(width, radius, SM_AGG_SGM, p1, p2, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def sgm_workspace_bytes(width: int, height: int, num_disp: int, radius: int, p2: int = 0) -> int:
+    """Bytes of device workspace one 'sgm' frame takes on its handle (sm_sgm_workspace_bytes, host-only)."""
+    n = ctypes.c_size_t()
+    _capi.check(_capi.load().sm_sgm_workspace_bytes(width, height, num_disp, radius, p2, ctypes.byref(n)))
+    return n.value
 
 
 def _check_out(out_t, shape, dtype, device, name: str = "out_t"):
@@ -135,6 +153,12 @@ class BlockMatcher:
 
     def set_guided_eps(self, eps: float):
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_GUIDED_EPS, float(eps)))
+
+    def set_sgm_penalties(self, p1: int = 0, p2: int = 0):
+        """Penalties of agg='sgm' (SM_PARAM_SGM_P1 / _P2): integers, 0 = auto (8 win^2 / 32 win^2 of the
+        call's window).  P1 <= P2 and 255 win^2 + P2 <= 65535 are checked by the matching call."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P1, float(int(p1))))
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P2, float(int(p2))))
 
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
                         lr_check: bool = False) -> np.ndarray:
@@ -570,6 +594,11 @@ class BlockMatcherGroup:
 
     def set_guided_eps(self, eps: float):
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_GUIDED_EPS, float(eps)))
+
+    def set_sgm_penalties(self, p1: int = 0, p2: int = 0):
+        """BlockMatcher.set_sgm_penalties on every member (agg='sgm' runs in match_batch only: whole frames)."""
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P1, float(int(p1))))
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P2, float(int(p2))))
 
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
               median: bool = False) -> np.ndarray:

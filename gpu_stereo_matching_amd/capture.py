@@ -142,7 +142,7 @@ def _main(argv=None) -> int:
     ap.add_argument("--radius", type=int, default=5, help="SADWindowSize (the window radius, Caller.cpp:19)")
     ap.add_argument("--disp", type=int, default=64, help="searchRange (number of disparities, Caller.cpp:19)")
     ap.add_argument("--batch", type=int, default=4)
-    ap.add_argument("--agg", default="box", choices=["box", "guided"])
+    ap.add_argument("--agg", default="box", choices=["box", "guided", "sgm"])
     ap.add_argument("--out", help="directory for disp_<n>.png")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)

@@ -122,6 +122,13 @@ inline bool wide_path(int radius, int W, int H, int pitch) {
 size_t literal_workspace_bytes(int D);
 hipError_t launch_device_cu_literal(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int radius, int D,
                                     uint32_t* ws, uint8_t* out, int opitch, hipStream_t s);
+// semi-global matching (bm_sgm.hip): the four paths' sum S u32 [D][H][W], zeroed by the caller, from the u16 SAD
+// volume (0 <= P1 <= P2, 255 * win^2 + P2 <= 65535), and the WTA over it: the left map (smallest existing d at
+// min S, no threshold) and, when right_keys is given, the right view's keys [H][W], min over the d whose pair
+// (u + d, d) exists of (S(u + d, d) << 8 | d)
+hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, uint32_t* S, hipStream_t s);
+hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
+                          hipStream_t s);
 // (2r+1)^2 median with replicate borders, radius 1..3 (bm_post.hip)
 hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
                          uint8_t* dst, int dpitch, int64_t dstride, hipStream_t s);

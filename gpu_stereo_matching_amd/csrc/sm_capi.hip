@@ -59,6 +59,7 @@ struct sm_handle {
     size_t bgr_bytes = 0;
     float guided_eps = 6.5025f;  // 1e-4 * 255^2 (AD units)
     int staged_group = 8;        // SM_STAGED frames per launch group (SM_PARAM_STAGED_GROUP)
+    int sgm_p1 = 0, sgm_p2 = 0;  // SM_AGG_SGM penalties (SM_PARAM_SGM_P1 / _P2), 0 = auto
     // host calls record the upload / match / download split (SM_PARAM_STAGE_TIMING): 0 off, 1 on, 2 auto
     // (default: on once sm_last_stage_ms has been called on the handle, or when SM_VERBOSE is set)
     int stage_timing = 2;
@@ -185,6 +186,68 @@ int ensure_vol(sm_handle* h, size_t bytes) {
     return SM_OK;
 }
 
+// ---- SM_AGG_SGM (bm_sgm.hip) ----
+// The argument rules of sm_sgm_check: every entry point that takes the flag goes through here.
+int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out) {
+    if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_AGG_SGM does not combine with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID (flags 0x%x)", flags);
+    if (radius < 0 || radius > sm::kMaxFastRadius)
+        return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: radius %d out of [0, %d] (the u16 SAD volume)", radius,
+                    sm::kMaxFastRadius);
+    if (width < 1 || width > 4096) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: width %d out of [1, 4096]", width);
+    if (p1 < 0 || p2 < 0) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: negative penalty (P1 %d, P2 %d)", p1, p2);
+    const int win2 = (2 * radius + 1) * (2 * radius + 1);
+    if (p1 == 0) p1 = 8 * win2;
+    if (p2 == 0) p2 = 32 * win2;
+    if (p1 > p2) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: P1 %d > P2 %d", p1, p2);
+    if (255 * win2 + p2 > 65535)
+        return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: 255 * win^2 + P2 = %d exceeds 65535 (16-bit path costs) at radius %d",
+                    255 * win2 + p2, radius);
+    if (p1_out) *p1_out = p1;
+    if (p2_out) *p2_out = p2;
+    return SM_OK;
+}
+
+// One frame's workspace in d_vol: [S u32 4PD, its head doubling as the u8 AD volume][SAD u16 2PD][right keys u32 4P]
+struct SgmWs {
+    size_t sad, rkeys, bytes;
+};
+SgmWs sgm_ws(int64_t P, int D) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    SgmWs w;
+    w.sad = up((size_t)(4 * P * D));
+    w.rkeys = w.sad + up((size_t)(2 * P * D));
+    w.bytes = w.rkeys + up((size_t)(4 * P));
+    return w;
+}
+
+// Left maps (and right maps, when right_map is given: dense W x H planes) of `batch` frames, one frame after
+// another through the volume workspace: AD -> SAD -> zeroed S -> four paths -> WTA.
+int run_sgm(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch, int64_t fstride,
+            int radius, int D, int p1, int p2, uint8_t* lmap, int lpitch, int64_t lstride, uint8_t* right_map,
+            hipStream_t s) {
+    const int64_t P = (int64_t)W * H;
+    const SgmWs w = sgm_ws(P, D);
+    const int rc = ensure_vol(h, w.bytes);   // the only allocation of the pass, before any launch
+    if (rc)
+        return fail(rc, "SM_AGG_SGM: no %zu-byte workspace for %dx%d D=%d (sm_sgm_workspace_bytes): %s", w.bytes, W, H, D,
+                    std::string(g_err).c_str());
+    uint8_t* ad = h->d_vol;
+    uint32_t* S = reinterpret_cast<uint32_t*>(h->d_vol);
+    uint16_t* sad = reinterpret_cast<uint16_t*>(h->d_vol + w.sad);
+    uint32_t* rkeys = right_map ? reinterpret_cast<uint32_t*>(h->d_vol + w.rkeys) : nullptr;
+    for (int f = 0; f < batch; ++f) {
+        SM_HIP(sm::launch_ad_volume(L + f * fstride, R + f * fstride, W, H, pitch, fstride, 1, D, ad, P * D, s));
+        SM_HIP(sm::launch_box_sad_volume(ad, W, H, radius, D, sad, s));
+        SM_HIP(hipMemsetAsync(S, 0, (size_t)(4 * P * D), s));
+        SM_HIP(sm::launch_sgm_paths(sad, W, H, D, p1, p2, S, s));
+        SM_HIP(sm::launch_sgm_wta(S, W, H, D, lmap + f * lstride, lpitch, rkeys, s));
+        if (right_map) SM_HIP(sm::launch_keys_low_byte(rkeys, P, right_map + f * P, s));
+    }
+    return SM_OK;
+}
+
 // Staged box path through AD (u8) + SAD (u16) volume workspaces, in launch groups of up to
 // kStagedGroup frames (workspace <= kStagedBytes): one AD, one SAD and one WTA launch per group, as
 // the fused path batches frames per launch.  The SAD launch sees the group's g*D planes as one
@@ -249,16 +312,22 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
                     int64_t fstride, int radius, int D, unsigned flags, uint8_t* disp, int opitch, int64_t ostride,
                     uint8_t* right_out, uint8_t* mask_out, int apitch, int64_t astride, hipStream_t s) {
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
+    const bool sgm = (flags & SM_AGG_SGM) != 0;
     const bool lr = (flags & SM_LR_CHECK) != 0 || right_out || mask_out;
     const bool med = (flags & SM_MEDIAN) != 0;
     constexpr int kMedianRadius = 3;   // MeanFilter(disp, disp, 3)
     const int64_t P = (int64_t)W * H;
     const int64_t PB = P * batch;
-    const bool fused_right = lr && !guided && radius <= sm::kMaxBoxRadius;
+    int sgm_p1 = 0, sgm_p2 = 0;
+    if (sgm) {   // before the other flags' checks: the combinations are its to reject
+        const int rc = sgm_check(W, radius, flags, h->sgm_p1, h->sgm_p2, &sgm_p1, &sgm_p2);
+        if (rc) return rc;
+    }
+    const bool fused_right = lr && !guided && !sgm && radius <= sm::kMaxBoxRadius;
     const bool guided_right = lr && guided;   // right view fused into the guided pass (bm_guided.hip)
     // box r > 15: the separable wide-window path (bm_wide.hip), right view included; wider frames keep the
     // direct generic kernel and the mirrored LR pass
-    const bool wide = !guided && sm::wide_path(radius, W, H, pitch);
+    const bool wide = !guided && !sgm && sm::wide_path(radius, W, H, pitch);
     if ((flags & SM_DEVICE_CU_GRID) != 0) {   // Device.cu's launch geometry, frame by frame (bm_literal.hip)
         if (flags != SM_DEVICE_CU_GRID || lr)
             return fail(SM_ERR_INVALID_ARG, "SM_DEVICE_CU_GRID is box aggregation only (flags 0x%x)", flags);
@@ -282,7 +351,7 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
     }
 
     // workspace: [left raw (med)] [right (lr)] [right filtered (lr && med)] [mirrored L, R (lr, not fused)]
-    const bool mirrored = lr && !fused_right && !guided_right && !wide;
+    const bool mirrored = lr && !fused_right && !guided_right && !wide && !sgm;
     const int64_t n_planes = (med ? 1 : 0) + (lr ? 1 : 0) + (lr && med ? 1 : 0) + (mirrored ? 2 : 0);
     if (n_planes > 0) {
         int rc = ensure_lr(h, (size_t)(n_planes * PB));
@@ -320,7 +389,11 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
     a.out_frame_stride = lstride;
     a.keys = nullptr;
     a.rpart = nullptr;
-    if (fused_right) {
+    if (sgm) {   // the right view comes from the same sum volume as the left map (bm_sgm.hip)
+        int rc = run_sgm(h, L, R, W, H, pitch, batch, fstride, radius, D, sgm_p1, sgm_p2, lmap, lpitch, lstride,
+                         lr ? right_map : nullptr, s);
+        if (rc) return rc;
+    } else if (fused_right) {
         int rc = ensure_rpart(h, sm::box_right_partial_bytes(W, H, radius, D, batch));
         if (rc) return rc;
         a.rpart = h->d_rpart;
@@ -414,7 +487,7 @@ bool scratch_event_forced() {
 int run_device(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
                int64_t fstride, int radius, int D, unsigned flags, uint8_t* disp, int opitch, int64_t ostride,
                uint8_t* right_out, uint8_t* mask_out, int apitch, int64_t astride, hipStream_t s) {
-    const bool uses_ws = (flags & (SM_STAGED | SM_MEDIAN | SM_LR_CHECK | SM_DEVICE_CU_GRID)) != 0 || right_out || mask_out ||
+    const bool uses_ws = (flags & (SM_STAGED | SM_MEDIAN | SM_LR_CHECK | SM_DEVICE_CU_GRID | SM_AGG_SGM)) != 0 || right_out || mask_out ||
                          (!(flags & SM_AGG_GUIDED) && sm::wide_path(radius, W, H, pitch)) || scratch_event_forced();
     if (uses_ws && h->scratch_pending && h->scratch_stream != s) SM_HIP(hipStreamWaitEvent(s, h->scratch_ev, 0));
     const int rc = run_device_body(h, L, R, W, H, pitch, batch, fstride, radius, D, flags, disp, opitch, ostride,
@@ -1031,6 +1104,9 @@ int group_bands(sm_group* g, const uint8_t* left, const uint8_t* right, int widt
     if (!left || !right || !disp_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if (flags & SM_DEVICE_CU_GRID)   // the literal grid is anchored at the frame's corner: not row-local
         return fail(SM_ERR_INVALID_ARG, "SM_DEVICE_CU_GRID needs whole frames (sm_group_block_match_batch_u8)");
+    if (flags & SM_AGG_SGM)   // the vertical paths run through every row of the frame
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_AGG_SGM needs whole frames: its vertical paths cross the row bands (sm_group_block_match_batch_u8)");
     if (width <= 0 || height <= 0 || pitch < width || out_pitch < width)
         return fail(SM_ERR_INVALID_ARG, "bad frame geometry %dx%d pitch %d out_pitch %d", width, height, pitch,
                     out_pitch);
@@ -1169,8 +1245,30 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         if (h->stage_timing == 2) h->stage_requested = false;   // back to the default: unarmed until read
         return SM_OK;
     }
-
+    if (param == SM_PARAM_SGM_P1 || param == SM_PARAM_SGM_P2) {
+        const int v = (int)value;
+        if (!(value >= 0.f) || value > 65535.f || (float)v != value)
+            return fail(SM_ERR_INVALID_ARG, "SGM penalty must be an integer in [0, 65535] (0 = auto)");
+        (param == SM_PARAM_SGM_P1 ? h->sgm_p1 : h->sgm_p2) = v;
+        return SM_OK;
+    }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);
+}
+
+SM_API int sm_sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out) {
+    return sgm_check(width, radius, flags, p1, p2, p1_out, p2_out);
+}
+
+SM_API int sm_sgm_workspace_bytes(int width, int height, int num_disp, int radius, int p2, size_t* bytes) {
+    if (!bytes) return fail(SM_ERR_INVALID_ARG, "null bytes pointer");
+    *bytes = 0;
+    if (height < 1) return fail(SM_ERR_INVALID_ARG, "bad frame height %d", height);
+    if (num_disp < 1 || num_disp > sm::kMaxDisp)
+        return fail(SM_ERR_INVALID_ARG, "num_disp %d out of [1,%d]", num_disp, sm::kMaxDisp);
+    const int rc = sgm_check(width, radius, SM_AGG_SGM, 0, p2, nullptr, nullptr);
+    if (rc) return rc;
+    *bytes = sgm_ws((int64_t)width * height, num_disp).bytes;
+    return SM_OK;
 }
 
 SM_API int sm_host_alloc(size_t bytes, void** out) {
@@ -1308,6 +1406,8 @@ SM_API int sm_slice_keys_lr_device(sm_handle* h, const uint8_t* d_left, const ui
                                    void* d_right_keys, void* stream) {
     int rc = check_geometry(h, width, height, pitch, radius, d_hi > 0 ? d_hi : 1);
     if (rc) return rc;
+    if (flags & SM_AGG_SGM)
+        return fail(SM_ERR_INVALID_ARG, "slice LR keys: SM_AGG_SGM's recursion over d crosses the slices");
     if ((flags & ~(unsigned)SM_AGG_GUIDED) != 0u)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: flags 0x%x (SM_AGG_BOX or SM_AGG_GUIDED)", flags);
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
@@ -1882,6 +1982,8 @@ SM_API int sm_group_dslice_block_match_u8(sm_group* g, const uint8_t* left, cons
     if (width <= 0 || height <= 0 || pitch < width || out_pitch < width)
         return fail(SM_ERR_INVALID_ARG, "bad frame geometry %dx%d pitch %d out_pitch %d", width, height, pitch,
                     out_pitch);
+    if (flags & SM_AGG_SGM)
+        return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_AGG_SGM's recursion over d crosses the slices");
     if ((flags & ~(unsigned)(SM_AGG_GUIDED | SM_LR_CHECK)) != 0u)
         return fail(SM_ERR_INVALID_ARG,
                     "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK; no median, staged)", flags);
@@ -1949,6 +2051,8 @@ SM_API int sm_dslice_rehearse_u8(sm_handle* h, const uint8_t* left, const uint8_
     if (!left || !right || !disp_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
     if (members < 1 || members > 64) return fail(SM_ERR_INVALID_ARG, "members %d out of [1, 64]", members);
+    if (flags & SM_AGG_SGM)
+        return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_AGG_SGM's recursion over d crosses the slices");
     if ((flags & ~(unsigned)(SM_AGG_GUIDED | SM_LR_CHECK)) != 0u)
         return fail(SM_ERR_INVALID_ARG, "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK)",
                     flags);

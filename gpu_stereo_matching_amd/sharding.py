@@ -351,6 +351,8 @@ def band_disparity(matcher, left_t, right_t, radius: int, num_disp: int, y0: int
                    lr_check: bool = False, stream=None, median: bool = False):
     """Disparity rows [y0, y1) of an [H, W] device frame, matched from those rows plus the halo."""
     import torch
+    if agg == "sgm":   # its vertical paths run through every row: no halo makes a band's rows the frame's
+        raise ValueError("agg 'sgm' needs whole frames: it cannot be row-sharded")
     H = left_t.shape[-2]
     ys, ye = band_input_rows(H, y0, y1, band_halo(radius, agg, median))
     if stream is not None:   # the frames were written on the current stream

@@ -60,7 +60,7 @@ enum {
                                ~0.8 GB with groups of 1.  Lowering SM_PARAM_STAGED_GROUP frees the
                                workspace (after the handle's pending work), so the next staged call
                                allocates the smaller size */
-    SM_DEVICE_CU_GRID = 16u /* opt-in emulation of Device.cu's fixed launch geometry (Device.cu:231-233,
+    SM_DEVICE_CU_GRID = 16u,/* opt-in emulation of Device.cu's fixed launch geometry (Device.cu:231-233,
                                253): the AD cost only for rows < 256 and cols < 320, 0 elsewhere (the
                                memset, :193-194), and the all-zero map for width > 1024 (the failed
                                <<<rows, cols>>> launch, :191-192).  Equals the default map at exactly
@@ -68,6 +68,25 @@ enum {
                                out of bounds) is SM_ERR_INVALID_ARG.  Box aggregation only (no other flag);
                                whole frames only (not the row-band or d-slice group calls).  Uses
                                ~330 KB * num_disp of the handle's volume workspace */
+    SM_AGG_SGM = 32u        /* semi-global matching (this build's extension) on the box SAD cost C(d, y, x) (the
+                               zero-padded (2r+1)^2 SAD of sm_sad_volume_device), radius <= 7, width <= 4096.  Over
+                               the pairs that exist, x + d <= W (Device.cu:44), and the four directions rho =
+                               (+-1, 0), (0, +-1), with q = p - rho:
+                                 L(p, d) = C(p, d)                                          q outside the image
+                                 L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + P1, L(q, d+1) + P1, M + P2) - M,
+                                 M = min_k L(q, k);   S = sum of the four L.
+                               Left map: the smallest existing d at min S, no 50*win^2 threshold (S is no SAD).
+                               Right view (SM_LR_CHECK): S_R(u, d) = S(u + d, d) over the d whose pair (u + d, d)
+                               exists (u + 2d <= W), first minimum; then the usual check.  SM_MEDIAN filters both
+                               maps before the check.  Integer throughout: 0 <= P1 <= P2 and
+                               255 * win^2 + P2 <= 65535 (every L fits 16 bits), else SM_ERR_INVALID_ARG; penalties
+                               from SM_PARAM_SGM_P1 / _P2.  Frames of a batch run one after another through
+                               sm_sgm_workspace_bytes() of the handle's volume workspace (6 B per pixel and
+                               disparity: ~1.6 GB at 1080p D=128).  Honoured by sm_block_match_u8, _lr_u8, _bgr_u8,
+                               sm_match_device and sm_group_block_match_batch_u8.  SM_ERR_INVALID_ARG with
+                               SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID, and in the row-band group calls
+                               (vertical paths cross the bands), the d-slice calls and the slice-key calls (the
+                               recursion over d crosses the slices) */
 };
 
 /* ---- scalar parameters (sm_set_param_f) ---- */
@@ -75,13 +94,18 @@ enum {
     SM_PARAM_GUIDED_EPS = 1,  /* guided-filter epsilon in AD^2 units (default 6.5025 = 1e-4 * 255^2) */
     SM_PARAM_STAGED_GROUP = 2, /* SM_STAGED frames per launch group, 1..8 (default 8): bounds the
                                   handle's staged workspace (see SM_STAGED) */
-    SM_PARAM_STAGE_TIMING = 3  /* whether host calls record the upload / match / download split read by
+    SM_PARAM_STAGE_TIMING = 3, /* whether host calls record the upload / match / download split read by
                                   sm_last_stage_ms with two hipEvents (each a marker between the copy and
                                   compute queues, ~10 us per 1080p call together).  2 (default, auto):
                                   recorded once sm_last_stage_ms has been called on the handle (the calls
                                   after that first read), or in every call when the environment sets
                                   SM_VERBOSE; 1: always; 0: never, and sm_last_stage_ms reports 0.
                                   Setting 2 again returns to the unarmed default */
+    SM_PARAM_SGM_P1 = 4,       /* SM_AGG_SGM penalty of a disparity step of 1: an integer >= 0, 0 (default) =
+                                  auto, 8 * win^2 */
+    SM_PARAM_SGM_P2 = 5        /* SM_AGG_SGM penalty of a larger step: an integer >= 0, 0 (default) = auto,
+                                  32 * win^2.  P1 <= P2 and 255 * win^2 + P2 <= 65535 are checked by the matching
+                                  call, against its radius (sm_sgm_check) */
 };
 
 typedef struct sm_handle sm_handle;
@@ -98,6 +122,17 @@ SM_API int sm_create(int device, int max_width, int max_height, int max_disp, sm
 SM_API int sm_destroy(sm_handle *h);
 SM_API int sm_set_param_f(sm_handle *h, int param, float value);
 
+/* SM_AGG_SGM's argument rules, host-only (no device, no handle): resolves the penalties (0 = auto: P1 =
+ * 8 * win^2, P2 = 32 * win^2) into *p1_out / *p2_out (either may be NULL) and returns SM_ERR_INVALID_ARG, with a
+ * message naming the reason, for radius outside 0..7, width outside 1..4096, a negative penalty, P1 > P2,
+ * 255 * win^2 + P2 > 65535, or `flags` combining SM_AGG_SGM with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID.
+ * The matching entry points apply exactly this check. */
+SM_API int sm_sgm_check(int width, int radius, unsigned flags, int p1, int p2, int *p1_out, int *p2_out);
+/* Bytes of the handle's volume workspace one SM_AGG_SGM frame takes (host-only): the u32 sum volume S (whose
+ * first bytes hold the u8 AD volume until the SAD volume is built), the u16 SAD volume and the right view's
+ * u32 keys, 6 * P * num_disp + 4 * P plus alignment.  p2 (0 = auto) is checked as by sm_sgm_check. */
+SM_API int sm_sgm_workspace_bytes(int width, int height, int num_disp, int radius, int p2, size_t *bytes);
+
 /* Page-locked host memory for frames and maps (hipHostMalloc, portable).  The host entry points
  * take any host pointer; with buffers from here their copies run as DMA straight from / into the
  * caller's memory instead of through the runtime's pageable bounce buffers (the reference's
@@ -108,7 +143,7 @@ SM_API int sm_host_free(void *p);
 /* Host-pointer entry point — the blockMatching_gpu replacement.
  * left/right: uint8 gray, `height` rows of `width` bytes at row stride `pitch` (>= width).
  * disp_out: uint8, `height` rows at stride `out_pitch`.  Synchronous, like the reference.
- * flags: SM_AGG_BOX | SM_AGG_GUIDED, optionally | SM_LR_CHECK | SM_MEDIAN. */
+ * flags: SM_AGG_BOX | SM_AGG_GUIDED | SM_AGG_SGM, optionally | SM_LR_CHECK | SM_MEDIAN. */
 SM_API int sm_block_match_u8(sm_handle *h, const uint8_t *left, const uint8_t *right,
                              int width, int height, int pitch, int radius, int num_disp,
                              unsigned flags, uint8_t *disp_out, int out_pitch);

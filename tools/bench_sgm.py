@@ -1,0 +1,86 @@
+"""Time SM_AGG_SGM at 1080p, D = 128, r = 2 on the device-resident path (sm_match_device on torch tensors),
+without and with the LR check: hipEvents around `--iters` calls after `--warmup` calls, frames already in HBM.
+Writes profiles/sgm_bench.json: ms per frame, the algorithmic bytes of the design spelled out as a formula,
+and that traffic over the time as a fraction of the 6.85 TB/s fill rate the project measured
+(profiles/microbench/r05_write_ceiling.txt).  No GPU, no number: the script fails without one."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FILL_BYTES_PER_S = 6.85e12
+
+# per frame, P = W * H pixels, D disparities (bytes); an atomic add counts its read and its write
+FORMULA = {
+    "ad_volume": "2*P + P*D            (read the pair, write the u8 AD volume)",
+    "sad_volume": "P*D + 2*P*D          (read AD, write the u16 SAD volume)",
+    "zero_S": "4*P*D                (memset of the u32 sum volume)",
+    "paths_horizontal": "2 * (2*P*D + 8*P*D)  (per direction: read SAD u16, atomic-add S u32 = read + write)",
+    "paths_vertical": "2 * (2*P*D + 8*P*D)  (the same)",
+    "wta_left": "4*P*D + P            (read S, write the u8 map)",
+    "wta_right_lr_only": "4*P*D + 4*P + 4*P + P + 3*P  (read S along u + d, write and read the keys, write dR; the check reads two maps, writes one)",
+}
+
+
+def algorithmic_bytes(P, D, lr):
+    b = (2 * P + P * D) + 3 * P * D + 4 * P * D + 2 * 10 * P * D + 2 * 10 * P * D + (4 * P * D + P)
+    if lr:
+        b += 4 * P * D + 4 * P + 4 * P + P + 3 * P
+    return b
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--disp", type=int, default=128)
+    ap.add_argument("--radius", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sgm_bench.json"))
+    a = ap.parse_args(argv)
+    if a.iters < 20:
+        ap.error("--iters must be at least 20")
+    import torch
+    import gpu_stereo_matching_amd as sm
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_sgm: no GPU visible; nothing is measured on a CPU")
+    W, H, D, r = a.width, a.height, a.disp, a.radius
+    P = W * H
+    L, R = sm.synth_pair(1234, W, H, D)
+    Lt, Rt = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
+    out_t = torch.empty_like(Lt)
+    res = {"workload": {"width": W, "height": H, "num_disp": D, "radius": r, "penalties": sm.sgm_penalties(r)},
+           "device": torch.cuda.get_device_name(0), "warmup": a.warmup, "iters": a.iters,
+           "workspace_bytes": sm.sgm_workspace_bytes(W, H, D, r),
+           "algorithmic_bytes_formula": FORMULA, "fill_rate_bytes_per_s": FILL_BYTES_PER_S, "runs": {}}
+    with sm.BlockMatcher(0, W, H, D) as m:
+        for name, lr in (("sgm", False), ("sgm_lr", True)):
+            for _ in range(a.warmup):
+                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr)
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / a.iters
+            nbytes = algorithmic_bytes(P, D, lr)
+            res["runs"][name] = {"ms_per_frame": round(ms, 4), "algorithmic_bytes": nbytes,
+                                 "algorithmic_GB_per_s": round(nbytes / ms / 1e6, 1),
+                                 "fraction_of_fill_rate": round(nbytes / (ms * 1e-3) / FILL_BYTES_PER_S, 4),
+                                 "matched_pixels": int((out_t > 0).sum().item())}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
