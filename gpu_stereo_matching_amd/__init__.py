@@ -22,14 +22,14 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID, SM_AGG_SGM  # noqa: F401
+from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID, SM_AGG_SGM, SM_COST_CENSUS  # noqa: F401
 from .synth import synth_pair  # noqa: F401
 from .gray import bgr_to_gray  # noqa: F401
 
 __all__ = [
     "BlockMatcher", "BlockMatcherGroup", "blockMatching_gpu", "block_matching_gpu", "SMError", "synth_pair", "bgr_to_gray",
-    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
-    "sgm_penalties", "sgm_workspace_bytes",
+    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_COST_CENSUS", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
+    "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes",
 ]
 
 DEFAULT_GUIDED_EPS = 1e-4 * 255.0 * 255.0
@@ -46,23 +46,29 @@ def _as_u8_image(a, name: str) -> np.ndarray:
     return a if a.flags.c_contiguous else np.ascontiguousarray(a)
 
 
-def _flags(agg: str, lr_check: bool, median: bool = False) -> int:
-    """agg: 'box' (fused), 'box-staged' (through the AD / SAD volumes in HBM), 'guided', 'sgm' (four-path
+def _flags(agg: str, lr_check: bool, median: bool = False, cost: str = "ad") -> int:
+    """cost: 'ad' (absolute gray difference) or 'census' (SM_COST_CENSUS: Hamming distance of 9 x 7 census words;
+    agg 'box' or 'sgm', radius <= 7; the library rejects the other combinations with a reason).
+    agg: 'box' (fused), 'box-staged' (through the AD / SAD volumes in HBM), 'guided', 'sgm' (four-path
     semi-global matching on the box SAD volume, radius <= 7), or 'device-cu' (Device.cu's literal output with
     its fixed launch geometry: SM_DEVICE_CU_GRID, box only)."""
     if agg not in ("box", "guided", "box-staged", "device-cu", "sgm"):
         raise ValueError("agg must be 'box', 'box-staged', 'guided', 'sgm' or 'device-cu'")
+    if cost not in ("ad", "census"):
+        raise ValueError("cost must be 'ad' or 'census'")
     f = {"box": SM_AGG_BOX, "guided": SM_AGG_GUIDED, "box-staged": SM_AGG_BOX | SM_STAGED,
          "device-cu": SM_DEVICE_CU_GRID, "sgm": SM_AGG_SGM}[agg]
-    return f | (SM_LR_CHECK if lr_check else 0) | (SM_MEDIAN if median else 0)
+    return f | (SM_LR_CHECK if lr_check else 0) | (SM_MEDIAN if median else 0) | (SM_COST_CENSUS if cost == "census" else 0)
 
 
-def sgm_penalties(radius: int, p1: int = 0, p2: int = 0, width: int = 1) -> Tuple[int, int]:
+def sgm_penalties(radius: int, p1: int = 0, p2: int = 0, width: int = 1, cost: str = "ad") -> Tuple[int, int]:
     """The (P1, P2) an 'sgm' match at `radius` uses for the parameter values p1, p2 (0 = auto: 8 win^2 and
-    32 win^2), through the library's own argument check (sm_sgm_check, host-only); raises SMError where
-    the match would (P1 > P2, 255 win^2 + P2 > 65535, radius > 7, width > 4096)."""
+    32 win^2; with cost='census' 10 win^2 and 120 win^2), through the library's own argument check
+    (sm_sgm_check, host-only); raises SMError where the match would (P1 > P2, 255 win^2 + P2 > 65535, or
+    62 win^2 + P2 > 65535 with the census cost, radius > 7, width > 4096)."""
     a, b = ctypes.c_int(), ctypes.c_int()
-    _capi.check(_capi.load().sm_sgm_check(width, radius, SM_AGG_SGM, p1, p2, ctypes.byref(a), ctypes.byref(b)))
+    _capi.check(_capi.load().sm_sgm_check(width, radius, _flags("sgm", False, False, cost), p1, p2, ctypes.byref(a),
+                                          ctypes.byref(b)))
     return a.value, b.value
 
 
@@ -70,6 +76,17 @@ def sgm_workspace_bytes(width: int, height: int, num_disp: int, radius: int, p2:
     """Bytes of device workspace one 'sgm' frame takes on its handle (sm_sgm_workspace_bytes, host-only)."""
     n = ctypes.c_size_t()
     _capi.check(_capi.load().sm_sgm_workspace_bytes(width, height, num_disp, radius, p2, ctypes.byref(n)))
+    return n.value
+
+
+def census_workspace_bytes(width: int, height: int, num_disp: int, radius: int, agg: str = "box") -> int:
+    """Bytes of device workspace one cost='census' frame takes on its handle for agg 'box' or 'sgm'
+    (sm_census_workspace_bytes, host-only), the two census images included."""
+    if agg not in ("box", "sgm"):
+        raise ValueError("agg must be 'box' or 'sgm'")
+    n = ctypes.c_size_t()
+    _capi.check(_capi.load().sm_census_workspace_bytes(width, height, num_disp, radius, _flags(agg, False, False, "census"),
+                                                       ctypes.byref(n)))
     return n.value
 
 
@@ -180,9 +197,10 @@ class BlockMatcher:
 
     # -- host-pointer path (blockMatching_gpu replacement) -------------------------------
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-              median: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+              median: bool = False, out: Optional[np.ndarray] = None, cost: str = "ad") -> np.ndarray:
         """median=True: 7x7 median of the WTA map(s) (STMatching MeanFilter(disp, disp, 3)), before the LR check.
-        out: optional contiguous uint8 [H, W] host buffer (e.g. pinned memory) to write the map into."""
+        out: optional contiguous uint8 [H, W] host buffer (e.g. pinned memory) to write the map into.
+        cost: 'ad' or 'census' (SM_COST_CENSUS, with agg 'box' or 'sgm')."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
         if L.shape != R.shape:
@@ -193,11 +211,11 @@ class BlockMatcher:
         elif out.dtype != np.uint8 or out.shape != (H, W) or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous uint8 array of the frame's shape")
         _capi.check(self._lib.sm_block_match_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
-                                                _flags(agg, lr_check, median), out.ctypes.data, W))
+                                                _flags(agg, lr_check, median, cost), out.ctypes.data, W))
         return out
 
-    def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False
-                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False,
+                 cost: str = "ad") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(checked disparity, right-view disparity, valid mask)."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
@@ -206,12 +224,12 @@ class BlockMatcher:
         rd = np.empty((H, W), np.uint8)
         mask = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_block_match_lr_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
-                                                   _flags(agg, True, median), out.ctypes.data, rd.ctypes.data,
+                                                   _flags(agg, True, median, cost), out.ctypes.data, rd.ctypes.data,
                                                    mask.ctypes.data, W))
         return out, rd, mask
 
     def match_bgr(self, left_bgr, right_bgr, radius: int, num_disp: int, agg: str = "box",
-                  lr_check: bool = False) -> np.ndarray:
+                  lr_check: bool = False, cost: str = "ad") -> np.ndarray:
         """imread -> cvtColor(BGR2GRAY) -> blockMatching_gpu in one call (Caller.cpp:12-19): HxWx3/4
         uint8 BGR(A) frames in, uint8 disparity out; the gray conversion runs on the GPU."""
         Lb = np.ascontiguousarray(left_bgr, dtype=np.uint8)
@@ -221,7 +239,7 @@ class BlockMatcher:
         H, W, C = Lb.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_block_match_bgr_u8(self._h, Lb.ctypes.data, Rb.ctypes.data, W, H, W * C, C, radius,
-                                                    num_disp, _flags(agg, lr_check), out.ctypes.data, W))
+                                                    num_disp, _flags(agg, lr_check, False, cost), out.ctypes.data, W))
         return out
 
     def segment_tree(self, left_bgr, right_bgr, max_level: int = 60, scale: int = 4, sigma: float = 0.1,
@@ -298,6 +316,56 @@ class BlockMatcher:
         _capi.check(self._lib.sm_ad_volume_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, num_disp,
                                               out.ctypes.data))
         return out
+
+    def census_volume(self, left, right, num_disp: int) -> np.ndarray:
+        """The Hamming volume of the census cost (sm_census_volume_u8): uint8 [num_disp, H, W], d-major,
+        popcount(censusL(y, x) ^ censusR(y, x - d)) for x >= d, 0 where x < d."""
+        L = _as_u8_image(left, "left")
+        R = _as_u8_image(right, "right")
+        if L.shape != R.shape:
+            raise ValueError("left/right sizes differ")
+        H, W = L.shape
+        out = np.empty((num_disp, H, W), np.uint8)
+        _capi.check(self._lib.sm_census_volume_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, num_disp,
+                                                  out.ctypes.data))
+        return out
+
+    def census_volume_device(self, left_t, right_t, num_disp: int, out_t=None, stream=None):
+        """Device form of :meth:`census_volume`: [H, W] uint8 cuda tensors whose rows may be strided
+        (stride(1) == 1, stride(0) >= W); uint8 [num_disp, H, W] out, async on `stream`."""
+        import torch
+        H, W = left_t.shape
+        if left_t.stride(1) != 1 or right_t.stride(1) != 1 or left_t.stride(0) != right_t.stride(0) \
+                or left_t.shape != right_t.shape:
+            raise ValueError("expected two [H, W] uint8 tensors of one shape and row stride")
+        if out_t is None:
+            out_t = torch.empty((num_disp, H, W), dtype=torch.uint8, device=left_t.device)
+        _check_out(out_t, (num_disp, H, W), torch.uint8, left_t.device)
+        _capi.check(self._lib.sm_census_volume_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H,
+                                                      left_t.stride(0), num_disp, out_t.data_ptr(),
+                                                      self._stream_ptr(stream)))
+        return out_t
+
+    def census_device(self, img_t, out_t=None, stream=None):
+        """The 9 x 7 census words of an [H, W] uint8 cuda tensor (rows may be strided: stride(1) == 1) as an int64
+        [H, W] tensor holding the uint64 bit patterns (62 bits used, so never negative); async on `stream`."""
+        import torch
+        if img_t.dtype != torch.uint8 or img_t.dim() != 2 or not img_t.is_cuda or img_t.stride(1) != 1:
+            raise ValueError("expected an [H, W] uint8 device tensor with unit column stride")
+        H, W = img_t.shape
+        if out_t is None:
+            out_t = torch.empty((H, W), dtype=torch.int64, device=img_t.device)
+        _check_out(out_t, (H, W), torch.int64, img_t.device)
+        _capi.check(self._lib.sm_census_device(self._h, img_t.data_ptr(), W, H, img_t.stride(0), out_t.data_ptr(),
+                                               self._stream_ptr(stream)))
+        return out_t
+
+    def census(self, img) -> np.ndarray:
+        """The census words of a host image: uint64 [H, W] (sm_census_device around an upload and a download)."""
+        import torch
+        I = _as_u8_image(img, "img")
+        t = torch.from_numpy(I).to(f"cuda:{self.device}")
+        return self.census_device(t).cpu().numpy().view(np.uint64)
 
     def all_sad(self, left, right, radius: int, num_disp: int) -> np.ndarray:
         """getAllSAD (BlockMatching.cpp:191-261) on the GPU: uint8 [H, W, num_disp] (pixel-major
@@ -435,8 +503,9 @@ class BlockMatcher:
         return ctypes.c_void_p(stream.cuda_stream)
 
     def match_device(self, left_t, right_t, radius: int, num_disp: int, out_t=None, agg: str = "box",
-                     lr_check: bool = False, stream=None, median: bool = False):
-        """left_t/right_t: uint8 cuda tensors [H, W] or [B, H, W] (contiguous). Async on `stream`."""
+                     lr_check: bool = False, stream=None, median: bool = False, cost: str = "ad"):
+        """left_t/right_t: uint8 cuda tensors [H, W] or [B, H, W] (contiguous). Async on `stream`.
+        cost='census': the frames of a batch run one after another through the handle's volume workspace."""
         import torch
         if left_t.dtype != torch.uint8 or right_t.dtype != torch.uint8:
             raise ValueError("expected uint8 tensors")
@@ -452,8 +521,8 @@ class BlockMatcher:
             out_t = torch.empty_like(left_t)
         _check_out(out_t, left_t.shape, torch.uint8, left_t.device)
         _capi.check(self._lib.sm_match_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, W, B, H * W,
-                                              radius, num_disp, _flags(agg, lr_check, median), out_t.data_ptr(), W, H * W,
-                                              self._stream_ptr(stream)))
+                                              radius, num_disp, _flags(agg, lr_check, median, cost), out_t.data_ptr(), W,
+                                              H * W, self._stream_ptr(stream)))
         return out_t
 
     def slice_keys_device(self, left_t, right_t, radius: int, d_lo: int, d_hi: int, keys_t=None, stream=None):
@@ -601,8 +670,9 @@ class BlockMatcherGroup:
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P2, float(int(p2))))
 
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-              median: bool = False) -> np.ndarray:
-        """One frame, row-banded over the group (sm_group_block_match_u8)."""
+              median: bool = False, cost: str = "ad") -> np.ndarray:
+        """One frame, row-banded over the group (sm_group_block_match_u8).  cost='census' needs whole frames
+        (match_batch): the library refuses it here and says why."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
         if L.shape != R.shape:
@@ -610,7 +680,7 @@ class BlockMatcherGroup:
         H, W = L.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_group_block_match_u8(self._g, L.ctypes.data, R.ctypes.data, W, H, W, radius,
-                                                      num_disp, _flags(agg, lr_check, median), out.ctypes.data, W))
+                                                      num_disp, _flags(agg, lr_check, median, cost), out.ctypes.data, W))
         return out
 
     def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False
@@ -644,7 +714,7 @@ class BlockMatcherGroup:
         return out
 
     def match_batch(self, lefts, rights, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-                    median: bool = False):
+                    median: bool = False, cost: str = "ad"):
         """A list of equal-size pairs; frame f runs on member f mod len(group)."""
         Ls = [_as_u8_image(a, "left") for a in lefts]
         Rs = [_as_u8_image(a, "right") for a in rights]
@@ -657,7 +727,7 @@ class BlockMatcherGroup:
         n = len(Ls)
         ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
         _capi.check(self._lib.sm_group_block_match_batch_u8(self._g, ptrs(Ls), ptrs(Rs), n, W, H, W, radius,
-                                                            num_disp, _flags(agg, lr_check, median), ptrs(outs), W))
+                                                            num_disp, _flags(agg, lr_check, median, cost), ptrs(outs), W))
         return outs
 
 

@@ -25,6 +25,7 @@ SM_MEDIAN = 4
 SM_STAGED = 8
 SM_DEVICE_CU_GRID = 16
 SM_AGG_SGM = 32
+SM_COST_CENSUS = 64
 
 SM_PARAM_GUIDED_EPS = 1
 SM_PARAM_STAGED_GROUP = 2
@@ -47,7 +48,8 @@ EXPORTED = (
     "sm_guided_keys_to_disp_device", "sm_segment_tree_match_bgr_u8", "sm_segment_tree_refined_bgr_u8",
     "sm_last_segment_tree_stats", "sm_last_segment_tree_arrays", "sm_host_alloc", "sm_host_free",
     "sm_dslice_plan", "sm_dslice_rehearse_u8", "sm_slice_keys_lr_device", "sm_right_keys_to_disp_device",
-    "sm_lr_check_device", "sm_sgm_check", "sm_sgm_workspace_bytes",
+    "sm_lr_check_device", "sm_sgm_check", "sm_sgm_workspace_bytes", "sm_census_workspace_bytes", "sm_census_device",
+    "sm_census_volume_device", "sm_census_volume_u8",
 )
 
 
@@ -133,6 +135,10 @@ def load(path: str = LIB_PATH):
     L.sm_lr_check_device.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, vp]
     L.sm_sgm_check.argtypes = [i, i, u, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.sm_sgm_workspace_bytes.argtypes = [i, i, i, i, i, ctypes.POINTER(ctypes.c_size_t)]
+    L.sm_census_workspace_bytes.argtypes = [i, i, i, i, u, ctypes.POINTER(ctypes.c_size_t)]
+    L.sm_census_device.argtypes = [vp, vp, i, i, i, vp, vp]
+    L.sm_census_volume_device.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
+    L.sm_census_volume_u8.argtypes = [vp, vp, vp, i, i, i, i, vp]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

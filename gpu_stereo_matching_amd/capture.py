@@ -77,7 +77,7 @@ def _write_png(path: str, disp: np.ndarray) -> None:
 
 def run_loop(source, matcher, radius: int = 5, num_disp: int = 64, rectify_maps=None, batch: int = 4,
              agg: str = "box", on_map: Optional[Callable[[int, np.ndarray], None]] = None,
-             out_dir: Optional[str] = None) -> List[int]:
+             out_dir: Optional[str] = None, cost: str = "ad") -> List[int]:
     """Match every pair of `source` (an iterable of ``(n, left_bgr, right_bgr)``, e.g. a PairSequence),
     `batch` pairs per GPU launch through FrameStream (BGR -> gray -> [rectify] -> match on the GPU).
     Returns the pair numbers in the order their maps were delivered (the input order).  A short last
@@ -106,7 +106,8 @@ def run_loop(source, matcher, radius: int = 5, num_disp: int = 64, rectify_maps=
         nonlocal fs
         H, W = ls[0].shape[:2]
         if fs is None:
-            fs = FrameStream(matcher, batch, W, H, radius, num_disp, agg=agg, bgr=True, rectify_maps=rectify_maps)
+            fs = FrameStream(matcher, batch, W, H, radius, num_disp, agg=agg, bgr=True, rectify_maps=rectify_maps,
+                             cost=cost)
         elif (fs.H, fs.W) != (H, W):
             raise ValueError(f"pair {ns[0]}: frame size {W}x{H} differs from the stream's {fs.W}x{fs.H}")
         while len(ls) < batch:
@@ -143,6 +144,8 @@ def _main(argv=None) -> int:
     ap.add_argument("--disp", type=int, default=64, help="searchRange (number of disparities, Caller.cpp:19)")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--agg", default="box", choices=["box", "guided", "sgm"])
+    ap.add_argument("--cost", default="ad", choices=["ad", "census"],
+                    help="matching cost: absolute difference, or census / Hamming (with --agg box or sgm, radius <= 7)")
     ap.add_argument("--out", help="directory for disp_<n>.png")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -157,7 +160,7 @@ def _main(argv=None) -> int:
     H, W = first[1].shape[:2]
     with BlockMatcher(a.device, W, H, max(a.disp, 1)) as m:
         maps = calib.rectify(m, *calib.load_data_batch(a.calib), (W, H)) if a.calib else None
-        done = run_loop(seq, m, a.radius, a.disp, rectify_maps=maps, batch=a.batch, agg=a.agg, out_dir=a.out,
+        done = run_loop(seq, m, a.radius, a.disp, rectify_maps=maps, batch=a.batch, agg=a.agg, out_dir=a.out, cost=a.cost,
                         on_map=lambda n, d: print(f"pair {n}: {W}x{H}, {int((d > 0).sum())} matched pixels"))
     print(f"{len(done)} pairs matched")
     return 0

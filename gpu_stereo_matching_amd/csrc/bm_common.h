@@ -129,6 +129,15 @@ hipError_t launch_device_cu_literal(const uint8_t* L, const uint8_t* R, int W, i
 hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, uint32_t* S, hipStream_t s);
 hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
                           hipStream_t s);
+// the same WTA, thresholdless, over a u16 cost volume [D][H][W] (SM_COST_CENSUS with SM_AGG_BOX)
+hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, uint8_t* disp, int out_pitch,
+                               uint32_t* right_keys, hipStream_t s);
+// census cost (bm_census.hip): the 9 x 7 census words u64 [H][W] of an image (replicated border, 62 bits), and
+// the Hamming volume u8 [D][H][W] of two census images, popcount(cL(y, x) ^ cR(y, x - d)) for x >= d, else 0:
+// the AD volume's layout, so launch_box_sad_volume sums it (<= 62 * win^2); W <= 4096
+hipError_t launch_census(const uint8_t* img, int W, int H, int pitch, uint64_t* census, hipStream_t s);
+hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, int H, int D, uint8_t* ham,
+                                hipStream_t s);
 // (2r+1)^2 median with replicate borders, radius 1..3 (bm_post.hip)
 hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
                          uint8_t* dst, int dpitch, int64_t dstride, hipStream_t s);

@@ -194,22 +194,25 @@ __global__ __launch_bounds__(1024) void sgm_v_kernel(const uint16_t* __restrict_
 // Left: the smallest existing d (d <= W - x) attaining min S, no threshold.  Right view: S_R(y, u, d) =
 // S(y, u + d, d) (StereoHelper.cpp:156-180) over the d whose pair (u + d, d) exists, u + 2 d <= W (which
 // implies u + d < W; d = 0 always exists); key = S << 8 | d, whose low byte is dR.
-__global__ __launch_bounds__(256) void sgm_wta_kernel(const uint32_t* __restrict__ S, int W, int H, int D,
+// T: uint32_t, the paths' sum S (< 2^18), or uint16_t, a box cost volume taken without SGM (SM_COST_CENSUS with
+// SM_AGG_BOX: the census cost, <= 62 * win^2 = 13950); either key fits 32 bits.
+template <typename T>
+__global__ __launch_bounds__(256) void sgm_wta_kernel(const T* __restrict__ S, int W, int H, int D,
                                                       uint8_t* __restrict__ disp, int pitch,
                                                       uint32_t* __restrict__ rkeys) {
     const int nxb = (W + 255) / 256;
     const int y = blockIdx.x / nxb, x = (blockIdx.x - y * nxb) * 256 + threadIdx.x;
     if (x >= W) return;
     const int64_t P = (int64_t)W * H;
-    const uint32_t* s = S + (int64_t)y * W + x;
+    const T* s = S + (int64_t)y * W + x;
     const int dmax = min(D - 1, W - x);
     uint32_t best = 0xFFFFFFFFu;
-    for (int d = 0; d <= dmax; ++d) best = min(best, (s[d * P] << 8) | (uint32_t)d);
+    for (int d = 0; d <= dmax; ++d) best = min(best, ((uint32_t)s[d * P] << 8) | (uint32_t)d);
     disp[(int64_t)y * pitch + x] = (uint8_t)(best & 0xFFu);
     if (rkeys) {
         const int rmax = min(D - 1, (W - x) / 2);
         uint32_t rb = 0xFFFFFFFFu;
-        for (int d = 0; d <= rmax; ++d) rb = min(rb, (s[d * P + d] << 8) | (uint32_t)d);
+        for (int d = 0; d <= rmax; ++d) rb = min(rb, ((uint32_t)s[d * P + d] << 8) | (uint32_t)d);
         rkeys[(int64_t)y * W + x] = rb;
     }
 }
@@ -248,12 +251,25 @@ hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, in
     return hipGetLastError();
 }
 
-hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
-                          hipStream_t s) {
+namespace {
+template <typename T>
+hipError_t launch_wta(const T* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys, hipStream_t s) {
     const int64_t blocks = (int64_t)((W + 255) / 256) * H;
     if (W <= 0 || H <= 0 || D < 1 || D > kMaxDisp || out_pitch < W || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sgm_wta_kernel, dim3((unsigned)blocks), dim3(256), 0, s, S, W, H, D, disp, out_pitch, right_keys);
+    hipLaunchKernelGGL(sgm_wta_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, S, W, H, D, disp, out_pitch,
+                       right_keys);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
+                          hipStream_t s) {
+    return launch_wta(S, W, H, D, disp, out_pitch, right_keys, s);
+}
+
+hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, uint8_t* disp, int out_pitch,
+                               uint32_t* right_keys, hipStream_t s) {
+    return launch_wta(C, W, H, D, disp, out_pitch, right_keys, s);
 }
 
 }  // namespace sm

@@ -186,9 +186,30 @@ int ensure_vol(sm_handle* h, size_t bytes) {
     return SM_OK;
 }
 
+// ---- SM_COST_CENSUS (bm_census.hip) ----
+// The argument rules of the census cost, for box and SGM alike: every entry point that takes the flag goes
+// through here (or through sgm_check, which starts with it).
+int census_check(int width, int radius, unsigned flags) {
+    if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_COST_CENSUS does not combine with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID (flags 0x%x)",
+                    flags);
+    if (radius < 0 || radius > sm::kMaxFastRadius)
+        return fail(SM_ERR_INVALID_ARG, "SM_COST_CENSUS: radius %d out of [0, %d] (the u16 cost volume)", radius,
+                    sm::kMaxFastRadius);
+    if (width < 1 || width > 4096) return fail(SM_ERR_INVALID_ARG, "SM_COST_CENSUS: width %d out of [1, 4096]", width);
+    return SM_OK;
+}
+
 // ---- SM_AGG_SGM (bm_sgm.hip) ----
-// The argument rules of sm_sgm_check: every entry point that takes the flag goes through here.
+// The argument rules of sm_sgm_check: every entry point that takes the flag goes through here.  With
+// SM_COST_CENSUS in `flags` the cost is at most 62 per pixel instead of 255, and the auto penalties follow it.
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out) {
+    const bool census = (flags & SM_COST_CENSUS) != 0;
+    if (census) {
+        const int rc = census_check(width, radius, flags);
+        if (rc) return rc;
+    }
     if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
         return fail(SM_ERR_INVALID_ARG,
                     "SM_AGG_SGM does not combine with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID (flags 0x%x)", flags);
@@ -198,12 +219,13 @@ int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out
     if (width < 1 || width > 4096) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: width %d out of [1, 4096]", width);
     if (p1 < 0 || p2 < 0) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: negative penalty (P1 %d, P2 %d)", p1, p2);
     const int win2 = (2 * radius + 1) * (2 * radius + 1);
-    if (p1 == 0) p1 = 8 * win2;
-    if (p2 == 0) p2 = 32 * win2;
+    if (p1 == 0) p1 = (census ? 10 : 8) * win2;
+    if (p2 == 0) p2 = (census ? 120 : 32) * win2;
     if (p1 > p2) return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: P1 %d > P2 %d", p1, p2);
-    if (255 * win2 + p2 > 65535)
-        return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: 255 * win^2 + P2 = %d exceeds 65535 (16-bit path costs) at radius %d",
-                    255 * win2 + p2, radius);
+    const int cmax = census ? 62 : 255;   // the largest cost of one pixel
+    if (cmax * win2 + p2 > 65535)
+        return fail(SM_ERR_INVALID_ARG, "SM_AGG_SGM: %d * win^2 + P2 = %d exceeds 65535 (16-bit path costs) at radius %d",
+                    cmax, cmax * win2 + p2, radius);
     if (p1_out) *p1_out = p1;
     if (p2_out) *p2_out = p2;
     return SM_OK;
@@ -222,23 +244,65 @@ SgmWs sgm_ws(int64_t P, int D) {
     return w;
 }
 
+// One SM_COST_CENSUS frame's workspace in d_vol.  SGM: sgm_ws with the two census images behind it (the Hamming
+// volume takes the AD volume's place at the head of S).  Box: [Hamming u8 PD][cost u16 2PD][right keys u32 4P]
+// [census L u64 8P][census R u64 8P].
+struct CensusWs {
+    size_t sad, rkeys, cl, cr, bytes;
+};
+CensusWs census_ws(int64_t P, int D, bool sgm) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    CensusWs w;
+    if (sgm) {
+        const SgmWs g = sgm_ws(P, D);
+        w.sad = g.sad;
+        w.rkeys = g.rkeys;
+        w.cl = g.bytes;
+    } else {
+        w.sad = up((size_t)(P * D));
+        w.rkeys = w.sad + up((size_t)(2 * P * D));
+        w.cl = w.rkeys + up((size_t)(4 * P));
+    }
+    w.cr = w.cl + up((size_t)(8 * P));
+    w.bytes = w.cr + up((size_t)(8 * P));
+    return w;
+}
+
+// The census words of both frames and their Hamming volume, into the workspace laid out by census_ws.
+int census_cost(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int D, uint8_t* vol, const CensusWs& w,
+                hipStream_t s) {
+    uint64_t* cl = reinterpret_cast<uint64_t*>(vol + w.cl);
+    uint64_t* cr = reinterpret_cast<uint64_t*>(vol + w.cr);
+    SM_HIP(sm::launch_census(L, W, H, pitch, cl, s));
+    SM_HIP(sm::launch_census(R, W, H, pitch, cr, s));
+    SM_HIP(sm::launch_census_volume(cl, cr, W, H, D, vol, s));
+    return SM_OK;
+}
+
 // Left maps (and right maps, when right_map is given: dense W x H planes) of `batch` frames, one frame after
-// another through the volume workspace: AD -> SAD -> zeroed S -> four paths -> WTA.
+// another through the volume workspace: AD (or census + Hamming) -> SAD -> zeroed S -> four paths -> WTA.
 int run_sgm(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch, int64_t fstride,
-            int radius, int D, int p1, int p2, uint8_t* lmap, int lpitch, int64_t lstride, uint8_t* right_map,
-            hipStream_t s) {
+            int radius, int D, int p1, int p2, bool census, uint8_t* lmap, int lpitch, int64_t lstride,
+            uint8_t* right_map, hipStream_t s) {
     const int64_t P = (int64_t)W * H;
     const SgmWs w = sgm_ws(P, D);
-    const int rc = ensure_vol(h, w.bytes);   // the only allocation of the pass, before any launch
+    const CensusWs cw = census_ws(P, D, true);
+    const size_t bytes = census ? cw.bytes : w.bytes;
+    const int rc = ensure_vol(h, bytes);   // the only allocation of the pass, before any launch
     if (rc)
-        return fail(rc, "SM_AGG_SGM: no %zu-byte workspace for %dx%d D=%d (sm_sgm_workspace_bytes): %s", w.bytes, W, H, D,
-                    std::string(g_err).c_str());
+        return fail(rc, "SM_AGG_SGM: no %zu-byte workspace for %dx%d D=%d (%s): %s", bytes, W, H, D,
+                    census ? "sm_census_workspace_bytes" : "sm_sgm_workspace_bytes", std::string(g_err).c_str());
     uint8_t* ad = h->d_vol;
     uint32_t* S = reinterpret_cast<uint32_t*>(h->d_vol);
     uint16_t* sad = reinterpret_cast<uint16_t*>(h->d_vol + w.sad);
     uint32_t* rkeys = right_map ? reinterpret_cast<uint32_t*>(h->d_vol + w.rkeys) : nullptr;
     for (int f = 0; f < batch; ++f) {
-        SM_HIP(sm::launch_ad_volume(L + f * fstride, R + f * fstride, W, H, pitch, fstride, 1, D, ad, P * D, s));
+        if (census) {
+            const int rcc = census_cost(L + f * fstride, R + f * fstride, W, H, pitch, D, h->d_vol, cw, s);
+            if (rcc) return rcc;
+        } else {
+            SM_HIP(sm::launch_ad_volume(L + f * fstride, R + f * fstride, W, H, pitch, fstride, 1, D, ad, P * D, s));
+        }
         SM_HIP(sm::launch_box_sad_volume(ad, W, H, radius, D, sad, s));
         SM_HIP(hipMemsetAsync(S, 0, (size_t)(4 * P * D), s));
         SM_HIP(sm::launch_sgm_paths(sad, W, H, D, p1, p2, S, s));
@@ -246,6 +310,36 @@ int run_sgm(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int 
         if (right_map) SM_HIP(sm::launch_keys_low_byte(rkeys, P, right_map + f * P, s));
     }
     return SM_OK;
+}
+
+// SM_AGG_BOX | SM_COST_CENSUS: the same, without the paths: census -> Hamming -> cost volume -> thresholdless WTA
+// over the u16 costs (left map, and the right view's keys from C(u + d, d)).
+int run_census_box(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
+                   int64_t fstride, int radius, int D, uint8_t* lmap, int lpitch, int64_t lstride, uint8_t* right_map,
+                   hipStream_t s) {
+    const int64_t P = (int64_t)W * H;
+    const CensusWs w = census_ws(P, D, false);
+    const int rc = ensure_vol(h, w.bytes);   // the only allocation of the pass, before any launch
+    if (rc)
+        return fail(rc, "SM_COST_CENSUS: no %zu-byte workspace for %dx%d D=%d (sm_census_workspace_bytes): %s", w.bytes,
+                    W, H, D, std::string(g_err).c_str());
+    uint16_t* cost = reinterpret_cast<uint16_t*>(h->d_vol + w.sad);
+    uint32_t* rkeys = right_map ? reinterpret_cast<uint32_t*>(h->d_vol + w.rkeys) : nullptr;
+    for (int f = 0; f < batch; ++f) {
+        const int rcc = census_cost(L + f * fstride, R + f * fstride, W, H, pitch, D, h->d_vol, w, s);
+        if (rcc) return rcc;
+        SM_HIP(sm::launch_box_sad_volume(h->d_vol, W, H, radius, D, cost, s));
+        SM_HIP(sm::launch_cost_wta_u16(cost, W, H, D, lmap + f * lstride, lpitch, rkeys, s));
+        if (right_map) SM_HIP(sm::launch_keys_low_byte(rkeys, P, right_map + f * P, s));
+    }
+    return SM_OK;
+}
+
+// What an entry point that honours SM_COST_CENSUS checks before it touches the device.
+int cost_check(const sm_handle* h, int width, int radius, unsigned flags) {
+    if (!(flags & SM_COST_CENSUS)) return SM_OK;
+    if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, nullptr, nullptr);
+    return census_check(width, radius, flags);
 }
 
 // Staged box path through AD (u8) + SAD (u16) volume workspaces, in launch groups of up to
@@ -313,6 +407,7 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
                     uint8_t* right_out, uint8_t* mask_out, int apitch, int64_t astride, hipStream_t s) {
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
     const bool sgm = (flags & SM_AGG_SGM) != 0;
+    const bool census = (flags & SM_COST_CENSUS) != 0;
     const bool lr = (flags & SM_LR_CHECK) != 0 || right_out || mask_out;
     const bool med = (flags & SM_MEDIAN) != 0;
     constexpr int kMedianRadius = 3;   // MeanFilter(disp, disp, 3)
@@ -322,12 +417,16 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
     if (sgm) {   // before the other flags' checks: the combinations are its to reject
         const int rc = sgm_check(W, radius, flags, h->sgm_p1, h->sgm_p2, &sgm_p1, &sgm_p2);
         if (rc) return rc;
+    } else if (census) {
+        const int rc = census_check(W, radius, flags);
+        if (rc) return rc;
     }
-    const bool fused_right = lr && !guided && !sgm && radius <= sm::kMaxBoxRadius;
+    const bool volume = sgm || census;   // both maps come out of one cost volume in d_vol
+    const bool fused_right = lr && !guided && !volume && radius <= sm::kMaxBoxRadius;
     const bool guided_right = lr && guided;   // right view fused into the guided pass (bm_guided.hip)
     // box r > 15: the separable wide-window path (bm_wide.hip), right view included; wider frames keep the
     // direct generic kernel and the mirrored LR pass
-    const bool wide = !guided && !sgm && sm::wide_path(radius, W, H, pitch);
+    const bool wide = !guided && !volume && sm::wide_path(radius, W, H, pitch);
     if ((flags & SM_DEVICE_CU_GRID) != 0) {   // Device.cu's launch geometry, frame by frame (bm_literal.hip)
         if (flags != SM_DEVICE_CU_GRID || lr)
             return fail(SM_ERR_INVALID_ARG, "SM_DEVICE_CU_GRID is box aggregation only (flags 0x%x)", flags);
@@ -351,7 +450,7 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
     }
 
     // workspace: [left raw (med)] [right (lr)] [right filtered (lr && med)] [mirrored L, R (lr, not fused)]
-    const bool mirrored = lr && !fused_right && !guided_right && !wide && !sgm;
+    const bool mirrored = lr && !fused_right && !guided_right && !wide && !volume;
     const int64_t n_planes = (med ? 1 : 0) + (lr ? 1 : 0) + (lr && med ? 1 : 0) + (mirrored ? 2 : 0);
     if (n_planes > 0) {
         int rc = ensure_lr(h, (size_t)(n_planes * PB));
@@ -390,8 +489,12 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
     a.keys = nullptr;
     a.rpart = nullptr;
     if (sgm) {   // the right view comes from the same sum volume as the left map (bm_sgm.hip)
-        int rc = run_sgm(h, L, R, W, H, pitch, batch, fstride, radius, D, sgm_p1, sgm_p2, lmap, lpitch, lstride,
-                         lr ? right_map : nullptr, s);
+        int rc = run_sgm(h, L, R, W, H, pitch, batch, fstride, radius, D, sgm_p1, sgm_p2, census, lmap, lpitch,
+                         lstride, lr ? right_map : nullptr, s);
+        if (rc) return rc;
+    } else if (census) {   // box aggregation of the census cost (bm_census.hip)
+        int rc = run_census_box(h, L, R, W, H, pitch, batch, fstride, radius, D, lmap, lpitch, lstride,
+                                lr ? right_map : nullptr, s);
         if (rc) return rc;
     } else if (fused_right) {
         int rc = ensure_rpart(h, sm::box_right_partial_bytes(W, H, radius, D, batch));
@@ -487,7 +590,7 @@ bool scratch_event_forced() {
 int run_device(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
                int64_t fstride, int radius, int D, unsigned flags, uint8_t* disp, int opitch, int64_t ostride,
                uint8_t* right_out, uint8_t* mask_out, int apitch, int64_t astride, hipStream_t s) {
-    const bool uses_ws = (flags & (SM_STAGED | SM_MEDIAN | SM_LR_CHECK | SM_DEVICE_CU_GRID | SM_AGG_SGM)) != 0 || right_out || mask_out ||
+    const bool uses_ws = (flags & (SM_STAGED | SM_MEDIAN | SM_LR_CHECK | SM_DEVICE_CU_GRID | SM_AGG_SGM | SM_COST_CENSUS)) != 0 || right_out || mask_out ||
                          (!(flags & SM_AGG_GUIDED) && sm::wide_path(radius, W, H, pitch)) || scratch_event_forced();
     if (uses_ws && h->scratch_pending && h->scratch_stream != s) SM_HIP(hipStreamWaitEvent(s, h->scratch_ev, 0));
     const int rc = run_device_body(h, L, R, W, H, pitch, batch, fstride, radius, D, flags, disp, opitch, ostride,
@@ -586,6 +689,8 @@ int host_match_rows(sm_handle* h, const uint8_t* left, const uint8_t* right, int
     if (!left || !right || !disp_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
     if (keep0 < 0 || keep1 > height || keep0 >= keep1) return fail(SM_ERR_INVALID_ARG, "bad kept rows");
+    rc = cost_check(h, width, radius, flags);
+    if (rc) return rc;
     if (width > h->max_w || height > h->max_h || num_disp > h->max_d)
         return fail(SM_ERR_CAPACITY, "frame %dx%d/D=%d exceeds handle capacity %dx%d/D=%d", width, height, num_disp,
                     h->max_w, h->max_h, h->max_d);
@@ -1107,6 +1212,10 @@ int group_bands(sm_group* g, const uint8_t* left, const uint8_t* right, int widt
     if (flags & SM_AGG_SGM)   // the vertical paths run through every row of the frame
         return fail(SM_ERR_INVALID_ARG,
                     "SM_AGG_SGM needs whole frames: its vertical paths cross the row bands (sm_group_block_match_batch_u8)");
+    if (flags & SM_COST_CENSUS)   // a band's replicated border is not the frame's
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_COST_CENSUS needs whole frames: the census window's replicated border would differ at the "
+                    "band edges (sm_group_block_match_batch_u8)");
     if (width <= 0 || height <= 0 || pitch < width || out_pitch < width)
         return fail(SM_ERR_INVALID_ARG, "bad frame geometry %dx%d pitch %d out_pitch %d", width, height, pitch,
                     out_pitch);
@@ -1271,6 +1380,20 @@ SM_API int sm_sgm_workspace_bytes(int width, int height, int num_disp, int radiu
     return SM_OK;
 }
 
+SM_API int sm_census_workspace_bytes(int width, int height, int num_disp, int radius, unsigned flags, size_t* bytes) {
+    if (!bytes) return fail(SM_ERR_INVALID_ARG, "null bytes pointer");
+    *bytes = 0;
+    if (height < 1) return fail(SM_ERR_INVALID_ARG, "bad frame height %d", height);
+    if (num_disp < 1 || num_disp > sm::kMaxDisp)
+        return fail(SM_ERR_INVALID_ARG, "num_disp %d out of [1,%d]", num_disp, sm::kMaxDisp);
+    flags |= SM_COST_CENSUS;
+    const bool sgm = (flags & SM_AGG_SGM) != 0;
+    const int rc = sgm ? sgm_check(width, radius, flags, 0, 0, nullptr, nullptr) : census_check(width, radius, flags);
+    if (rc) return rc;
+    *bytes = census_ws((int64_t)width * height, num_disp, sgm).bytes;
+    return SM_OK;
+}
+
 SM_API int sm_host_alloc(size_t bytes, void** out) {
     if (!out) return fail(SM_ERR_INVALID_ARG, "null out pointer");
     *out = nullptr;
@@ -1336,6 +1459,8 @@ SM_API int sm_match_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch < width");
     if (batch > 1 && (frame_stride < (int64_t)pitch * height || out_frame_stride < (int64_t)out_pitch * height))
         return fail(SM_ERR_INVALID_ARG, "frame strides overlap");
+    rc = cost_check(h, width, radius, flags);
+    if (rc) return rc;
     SM_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     return run_device(h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp, flags, d_disp,
@@ -1408,6 +1533,8 @@ SM_API int sm_slice_keys_lr_device(sm_handle* h, const uint8_t* d_left, const ui
     if (rc) return rc;
     if (flags & SM_AGG_SGM)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: SM_AGG_SGM's recursion over d crosses the slices");
+    if (flags & SM_COST_CENSUS)
+        return fail(SM_ERR_INVALID_ARG, "slice LR keys: SM_COST_CENSUS is not built for d-slices (the AD cost only)");
     if ((flags & ~(unsigned)SM_AGG_GUIDED) != 0u)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: flags 0x%x (SM_AGG_BOX or SM_AGG_GUIDED)", flags);
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
@@ -1635,6 +1762,64 @@ SM_API int sm_ad_volume_u8(sm_handle* h, const uint8_t* left, const uint8_t* rig
     return SM_OK;
 }
 
+SM_API int sm_census_device(sm_handle* h, const uint8_t* d_img, int width, int height, int pitch, uint64_t* d_census,
+                            void* stream) {
+    if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
+    if (!d_img || !d_census || width <= 0 || height <= 0 || pitch < width)
+        return fail(SM_ERR_INVALID_ARG, "bad census arguments");
+    SM_HIP(hipSetDevice(h->device));
+    SM_HIP(sm::launch_census(d_img, width, height, pitch, d_census, (hipStream_t)stream));
+    return SM_OK;
+}
+
+SM_API int sm_census_volume_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
+                                   int pitch, int num_disp, uint8_t* d_ham, void* stream) {
+    if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
+    if (!d_left || !d_right || !d_ham || width <= 0 || height <= 0 || pitch < width || num_disp < 1 ||
+        num_disp > sm::kMaxDisp)
+        return fail(SM_ERR_INVALID_ARG, "bad census-volume arguments");
+    if (width > 4096)
+        return fail(SM_ERR_INVALID_ARG, "width %d exceeds the census-volume kernel's 4096 columns", width);
+    SM_HIP(hipSetDevice(h->device));
+    const size_t img = ((size_t)width * height * 8 + 255) & ~(size_t)255;
+    const int rc = ensure_vol(h, 2 * img);   // the two census images
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t* cl = reinterpret_cast<uint64_t*>(h->d_vol);
+    uint64_t* cr = reinterpret_cast<uint64_t*>(h->d_vol + img);
+    SM_HIP(sm::launch_census(d_left, width, height, pitch, cl, s));
+    SM_HIP(sm::launch_census(d_right, width, height, pitch, cr, s));
+    SM_HIP(sm::launch_census_volume(cl, cr, width, height, num_disp, d_ham, s));
+    return SM_OK;
+}
+
+SM_API int sm_census_volume_u8(sm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                               int num_disp, uint8_t* ham_out) {
+    int rc = check_geometry(h, width, height, pitch, 0, num_disp);
+    if (rc) return rc;
+    if (!left || !right || !ham_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
+    if (width > h->max_w || height > h->max_h || num_disp > h->max_d)
+        return fail(SM_ERR_CAPACITY, "frame %dx%d/D=%d exceeds handle capacity", width, height, num_disp);
+    if (width > 4096)
+        return fail(SM_ERR_INVALID_ARG, "width %d exceeds the census-volume kernel's 4096 columns", width);
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t need = (size_t)width * height * num_disp;
+    const size_t vol = (need + 255) & ~(size_t)255, img = ((size_t)width * height * 8 + 255) & ~(size_t)255;
+    rc = ensure_vol(h, vol + 2 * img);   // [Hamming volume][census L][census R]
+    if (rc) return rc;
+    uint64_t* cl = reinterpret_cast<uint64_t*>(h->d_vol + vol);
+    uint64_t* cr = reinterpret_cast<uint64_t*>(h->d_vol + vol + img);
+    SM_HIP(copy2d(h->d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, s));
+    SM_HIP(copy2d(h->d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, s));
+    SM_HIP(sm::launch_census(h->d_left, width, height, width, cl, s));
+    SM_HIP(sm::launch_census(h->d_right, width, height, width, cr, s));
+    SM_HIP(sm::launch_census_volume(cl, cr, width, height, num_disp, h->d_vol, s));
+    SM_HIP(hipMemcpyAsync(ham_out, h->d_vol, need, hipMemcpyDeviceToHost, s));
+    SM_HIP(hipStreamSynchronize(s));
+    return SM_OK;
+}
+
 SM_API int sm_sad_volume_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
                                 int pitch, int radius, int num_disp, uint16_t* d_sad, void* stream) {
     int rc = check_geometry(h, width, height, pitch, radius, num_disp);
@@ -1838,6 +2023,8 @@ SM_API int sm_block_match_bgr_u8(sm_handle* h, const uint8_t* left_bgr, const ui
     if (!left_bgr || !right_bgr || !disp_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if ((channels != 3 && channels != 4) || pitch < width * channels || out_pitch < width)
         return fail(SM_ERR_INVALID_ARG, "bad BGR layout");
+    rc = cost_check(h, width, radius, flags);
+    if (rc) return rc;
     if (width > h->max_w || height > h->max_h || num_disp > h->max_d)
         return fail(SM_ERR_CAPACITY, "frame exceeds handle capacity");
     SM_HIP(hipSetDevice(h->device));
@@ -1984,6 +2171,8 @@ SM_API int sm_group_dslice_block_match_u8(sm_group* g, const uint8_t* left, cons
                     out_pitch);
     if (flags & SM_AGG_SGM)
         return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_AGG_SGM's recursion over d crosses the slices");
+    if (flags & SM_COST_CENSUS)
+        return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_COST_CENSUS is not built for d-slices (the AD cost only)");
     if ((flags & ~(unsigned)(SM_AGG_GUIDED | SM_LR_CHECK)) != 0u)
         return fail(SM_ERR_INVALID_ARG,
                     "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK; no median, staged)", flags);
@@ -2053,6 +2242,8 @@ SM_API int sm_dslice_rehearse_u8(sm_handle* h, const uint8_t* left, const uint8_
     if (members < 1 || members > 64) return fail(SM_ERR_INVALID_ARG, "members %d out of [1, 64]", members);
     if (flags & SM_AGG_SGM)
         return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_AGG_SGM's recursion over d crosses the slices");
+    if (flags & SM_COST_CENSUS)
+        return fail(SM_ERR_INVALID_ARG, "d-slice mode: SM_COST_CENSUS is not built for d-slices (the AD cost only)");
     if ((flags & ~(unsigned)(SM_AGG_GUIDED | SM_LR_CHECK)) != 0u)
         return fail(SM_ERR_INVALID_ARG, "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK)",
                     flags);

@@ -68,7 +68,7 @@ enum {
                                out of bounds) is SM_ERR_INVALID_ARG.  Box aggregation only (no other flag);
                                whole frames only (not the row-band or d-slice group calls).  Uses
                                ~330 KB * num_disp of the handle's volume workspace */
-    SM_AGG_SGM = 32u        /* semi-global matching (this build's extension) on the box SAD cost C(d, y, x) (the
+    SM_AGG_SGM = 32u,       /* semi-global matching (this build's extension) on the box SAD cost C(d, y, x) (the
                                zero-padded (2r+1)^2 SAD of sm_sad_volume_device), radius <= 7, width <= 4096.  Over
                                the pairs that exist, x + d <= W (Device.cu:44), and the four directions rho =
                                (+-1, 0), (0, +-1), with q = p - rho:
@@ -87,6 +87,30 @@ enum {
                                SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID, and in the row-band group calls
                                (vertical paths cross the bands), the d-slice calls and the slice-key calls (the
                                recursion over d crosses the slices) */
+    SM_COST_CENSUS = 64u    /* census / Hamming matching cost (this build's extension) in place of the absolute
+                               difference of gray values, with SM_AGG_BOX or SM_AGG_SGM; radius <= 7, width <= 4096.
+                               Robust to exposure and gain differences between the cameras, and a bounded integer.
+                                 census(y, x): uint64.  The window is 9 wide x 7 high, dx in [-4, 4], dy in [-3, 3],
+                                   visited row-major (dy outer, dx inner), the centre skipped: 62 neighbours on bits
+                                   0..61 in that order, bits 62-63 zero.  A bit is 1 iff I(clamp(y + dy, 0, H - 1),
+                                   clamp(x + dx, 0, W - 1)) < I(y, x) (replicated border: any frame size is legal).
+                                 ham[d][y][x] = popcount(censusL(y, x) ^ censusR(y, x - d)) for x >= d, else 0
+                                   (<= 62; the layout and zero rule of sm_ad_volume_device).
+                                 C = the zero-padded (2r+1)^2 window sum of ham (<= 62 * win^2 = 13950 at r = 7).
+                               SM_AGG_BOX | SM_COST_CENSUS: the left map is the smallest existing d (x + d <= W) at
+                               min C, with no 50 * win^2 threshold (that threshold is in AD units); the right view
+                               (SM_LR_CHECK) is C_R(u, d) = C(u + d, d) over u + 2d <= W, first minimum: SM_AGG_SGM's
+                               rules, applied to C; then the usual check.  SM_MEDIAN filters both maps before the
+                               check.  SM_AGG_SGM | SM_COST_CENSUS: SM_AGG_SGM exactly, with C above in place of the
+                               AD box SAD; the auto penalties become P1 = 10 * win^2, P2 = 120 * win^2 and the bound
+                               62 * win^2 + P2 <= 65535 (sm_sgm_check with this bit in `flags`).  Frames of a batch
+                               run one after another through sm_census_workspace_bytes() of the handle's volume
+                               workspace (3 or 6 B per pixel and disparity, plus 20 B per pixel), allocated by the
+                               first call that takes the flag.  Honoured by sm_block_match_u8, _lr_u8, _bgr_u8,
+                               sm_match_device and sm_group_block_match_batch_u8.  SM_ERR_INVALID_ARG, before any
+                               device work, with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID, for radius > 7 or
+                               width > 4096, in the row-band group calls (the replicated border would differ at
+                               the band edges), and in the d-slice and slice-key calls */
 };
 
 /* ---- scalar parameters (sm_set_param_f) ---- */
@@ -126,12 +150,20 @@ SM_API int sm_set_param_f(sm_handle *h, int param, float value);
  * 8 * win^2, P2 = 32 * win^2) into *p1_out / *p2_out (either may be NULL) and returns SM_ERR_INVALID_ARG, with a
  * message naming the reason, for radius outside 0..7, width outside 1..4096, a negative penalty, P1 > P2,
  * 255 * win^2 + P2 > 65535, or `flags` combining SM_AGG_SGM with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID.
+ * With SM_COST_CENSUS in `flags` the autos are P1 = 10 * win^2, P2 = 120 * win^2 and the bound is
+ * 62 * win^2 + P2 <= 65535 (the census cost is at most 62 per pixel).
  * The matching entry points apply exactly this check. */
 SM_API int sm_sgm_check(int width, int radius, unsigned flags, int p1, int p2, int *p1_out, int *p2_out);
 /* Bytes of the handle's volume workspace one SM_AGG_SGM frame takes (host-only): the u32 sum volume S (whose
  * first bytes hold the u8 AD volume until the SAD volume is built), the u16 SAD volume and the right view's
  * u32 keys, 6 * P * num_disp + 4 * P plus alignment.  p2 (0 = auto) is checked as by sm_sgm_check. */
 SM_API int sm_sgm_workspace_bytes(int width, int height, int num_disp, int radius, int p2, size_t *bytes);
+/* Bytes of the handle's volume workspace one SM_COST_CENSUS frame takes (host-only).  `flags` chooses the
+ * aggregation (SM_COST_CENSUS is implied): SM_AGG_BOX, 3 * P * num_disp + 20 * P (the u8 Hamming volume, the u16
+ * cost volume, the right view's u32 keys and the two u64 census images); SM_AGG_SGM, sm_sgm_workspace_bytes + 16 * P
+ * (the Hamming volume lies in the head of S); each part 256-B aligned.  The arguments are checked as by the
+ * matching call (auto penalties for SM_AGG_SGM). */
+SM_API int sm_census_workspace_bytes(int width, int height, int num_disp, int radius, unsigned flags, size_t *bytes);
 
 /* Page-locked host memory for frames and maps (hipHostMalloc, portable).  The host entry points
  * take any host pointer; with buffers from here their copies run as DMA straight from / into the
@@ -143,7 +175,7 @@ SM_API int sm_host_free(void *p);
 /* Host-pointer entry point — the blockMatching_gpu replacement.
  * left/right: uint8 gray, `height` rows of `width` bytes at row stride `pitch` (>= width).
  * disp_out: uint8, `height` rows at stride `out_pitch`.  Synchronous, like the reference.
- * flags: SM_AGG_BOX | SM_AGG_GUIDED | SM_AGG_SGM, optionally | SM_LR_CHECK | SM_MEDIAN. */
+ * flags: SM_AGG_BOX | SM_AGG_GUIDED | SM_AGG_SGM, optionally | SM_LR_CHECK | SM_MEDIAN | SM_COST_CENSUS. */
 SM_API int sm_block_match_u8(sm_handle *h, const uint8_t *left, const uint8_t *right,
                              int width, int height, int pitch, int radius, int num_disp,
                              unsigned flags, uint8_t *disp_out, int out_pitch);
@@ -255,6 +287,20 @@ SM_API int sm_ad_volume_device(sm_handle *h, const uint8_t *d_left, const uint8_
                                int pitch, int num_disp, uint8_t *d_dif, void *stream);
 SM_API int sm_ad_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t *right, int width, int height,
                            int pitch, int num_disp, uint8_t *dif_out);
+
+/* ---- the census cost's two stages (SM_COST_CENSUS) ----
+ * sm_census_device: the census words of one image (`height` rows of `width` bytes at stride `pitch` >= width) as
+ * dense uint64 [height][width]; any frame size.
+ * sm_census_volume_*: ham[d][y][x] = popcount(censusL(y,x) ^ censusR(y,x-d)) for x >= d, else 0, as d-major planes
+ * [num_disp][height][width] of uint8 (<= 62): the shape and zero rule of sm_ad_volume_*, which they mirror.  Device
+ * form: d_ham holds num_disp*width*height bytes; the two census images go through 16 * P bytes of the handle's
+ * volume workspace.  Host form: synchronous, ham_out likewise.  width <= 4096. */
+SM_API int sm_census_device(sm_handle *h, const uint8_t *d_img, int width, int height, int pitch,
+                            uint64_t *d_census, void *stream);
+SM_API int sm_census_volume_device(sm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int width, int height,
+                                   int pitch, int num_disp, uint8_t *d_ham, void *stream);
+SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t *right, int width, int height,
+                               int pitch, int num_disp, uint8_t *ham_out);
 
 /* u16 SAD volume sad[d][y][x] = zero-padded (2r+1)^2 window sum of the AD plane d, radius <= 7
  * (the volume kernalFindAllSAD / getAllSAD build, Device.cu:67-103 / BlockMatching.cpp:191-261,

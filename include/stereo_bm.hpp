@@ -190,13 +190,15 @@ inline int block_matching(const M& h_left, const M& h_right, M& h_disparity, int
     // the stage lines read the upload / match / download split of this call only: the handle stays at the
     // auto default (no event markers) for testBM / getDisp / PreCal / getAllSAD
     // (a literal SM_DEVICE_CU_GRID call runs on e.h even when a group exists, so it is timed there: ADVICE r5)
-    // (so does SM_AGG_SGM, whose vertical paths cross the row bands and whose d recursion crosses the d-slices)
-    const unsigned whole = flags & (unsigned)(SM_DEVICE_CU_GRID | SM_AGG_SGM);
+    // (so do SM_AGG_SGM, whose vertical paths cross the row bands and whose d recursion crosses the d-slices, and
+    // SM_COST_CENSUS, whose replicated border would differ at the band edges and which has no d-slice form)
+    const unsigned whole = flags & (unsigned)(SM_DEVICE_CU_GRID | SM_AGG_SGM | SM_COST_CENSUS);
     const bool timed = stage_lines && !detail::quiet() && (!e.g || whole);
     if (timed) sm_set_param_f(e.h, SM_PARAM_STAGE_TIMING, 1.f);
     const auto t0 = std::chrono::steady_clock::now();
-    // Device.cu's literal launch geometry (SM_DEVICE_CU_GRID) and semi-global matching (SM_AGG_SGM, penalties
-    // through sm_set_param_f(engine handle, SM_PARAM_SGM_P1 / _P2)) are whole-frame passes: one device
+    // Device.cu's literal launch geometry (SM_DEVICE_CU_GRID), semi-global matching (SM_AGG_SGM, penalties
+    // through sm_set_param_f(engine handle, SM_PARAM_SGM_P1 / _P2)) and the census cost (SM_COST_CENSUS) are
+    // whole-frame passes: one device
     int rc = whole ? sm_block_match_u8(e.h, h_left.data, h_right.data, cols, rows,
                                      (int)detail::row_step(h_left), SADWindowSize, searchRange, flags,
                                      h_disparity.data, (int)detail::row_step(h_disparity))

@@ -2,7 +2,10 @@
 without and with the LR check: hipEvents around `--iters` calls after `--warmup` calls, frames already in HBM.
 Writes profiles/sgm_bench.json: ms per frame, the algorithmic bytes of the design spelled out as a formula,
 and that traffic over the time as a fraction of the 6.85 TB/s fill rate the project measured
-(profiles/microbench/r05_write_ceiling.txt).  No GPU, no number: the script fails without one."""
+(profiles/microbench/r05_write_ceiling.txt).  No GPU, no number: the script fails without one.
+
+--cost census times the census cost (SM_COST_CENSUS) under --agg sgm or box instead, beside AD SGM from the same run
+of the same build, and writes profiles/census_bench.json (ms per map only: DESIGN §18)."""
 import argparse
 import json
 import os
@@ -32,6 +35,45 @@ def algorithmic_bytes(P, D, lr):
     return b
 
 
+def time_ms(torch, m, Lt, Rt, r, D, out_t, warmup, iters, **kw):
+    for _ in range(warmup):
+        m.match_device(Lt, Rt, r, D, out_t=out_t, **kw)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        m.match_device(Lt, Rt, r, D, out_t=out_t, **kw)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def census_main(a, sm, torch, Lt, Rt, out_t):
+    """ms per map of the census cost under a.agg, without and with LR, and of AD SGM in the same run."""
+    W, H, D, r = a.width, a.height, a.disp, a.radius
+    res = {"workload": {"width": W, "height": H, "num_disp": D, "radius": r, "cost": "census", "agg": a.agg,
+                        "penalties": sm.sgm_penalties(r, cost="census") if a.agg == "sgm" else None},
+           "device": torch.cuda.get_device_name(0), "warmup": a.warmup, "iters": a.iters,
+           "workspace_bytes": sm.census_workspace_bytes(W, H, D, r, agg=a.agg), "runs": {}}
+    with sm.BlockMatcher(0, W, H, D) as m:
+        # two rounds, alternating the variants, so that a drift of the machine shows as a spread
+        for rnd in range(2):
+            for name, kw in ((f"census_{a.agg}", dict(agg=a.agg, cost="census", lr_check=False)),
+                             (f"census_{a.agg}_lr", dict(agg=a.agg, cost="census", lr_check=True)),
+                             ("ad_sgm", dict(agg="sgm", lr_check=False)),
+                             ("ad_sgm_lr", dict(agg="sgm", lr_check=True))):
+                ms = time_ms(torch, m, Lt, Rt, r, D, out_t, a.warmup, a.iters, **kw)
+                run = res["runs"].setdefault(name, {"ms_per_frame": []})
+                run["ms_per_frame"].append(round(ms, 4))
+                run["matched_pixels"] = int((out_t > 0).sum().item())
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--width", type=int, default=1920)
@@ -40,10 +82,16 @@ def main(argv=None):
     ap.add_argument("--radius", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sgm_bench.json"))
+    ap.add_argument("--cost", default="ad", choices=["ad", "census"])
+    ap.add_argument("--agg", default="sgm", choices=["sgm", "box"])
+    ap.add_argument("--out", default=None, help="default: profiles/sgm_bench.json, or census_bench.json with --cost census")
     a = ap.parse_args(argv)
     if a.iters < 20:
         ap.error("--iters must be at least 20")
+    if a.cost == "ad" and a.agg != "sgm":
+        ap.error("--agg box is timed with --cost census only (the AD box path is bench.py's)")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "sgm_bench.json" if a.cost == "ad" else "census_bench.json")
     import torch
     import gpu_stereo_matching_amd as sm
     if not torch.cuda.is_available():
@@ -53,6 +101,8 @@ def main(argv=None):
     L, R = sm.synth_pair(1234, W, H, D)
     Lt, Rt = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     out_t = torch.empty_like(Lt)
+    if a.cost == "census":
+        return census_main(a, sm, torch, Lt, Rt, out_t)
     res = {"workload": {"width": W, "height": H, "num_disp": D, "radius": r, "penalties": sm.sgm_penalties(r)},
            "device": torch.cuda.get_device_name(0), "warmup": a.warmup, "iters": a.iters,
            "workspace_bytes": sm.sgm_workspace_bytes(W, H, D, r),
