@@ -177,6 +177,12 @@ class BlockMatcher:
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P1, float(int(p1))))
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P2, float(int(p2))))
 
+    def set_box_kernel(self, kernel: int = 0):
+        """Which kernel the plain box pass runs (SM_PARAM_BOX_KERNEL): 0 auto by launch size, 1 the VALU kernels,
+        2 the matrix-pipe kernel, at every launch size; same maps and keys.  2 outside its scope (lr_check,
+        radius 0, radius >= 8) runs the VALU kernels."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_KERNEL, float(kernel)))
+
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
                         lr_check: bool = False) -> np.ndarray:
         """The d-slice split of BlockMatcherGroup.match_dslice with `members` members, run one after

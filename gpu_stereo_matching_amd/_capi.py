@@ -32,6 +32,7 @@ SM_PARAM_STAGED_GROUP = 2
 SM_PARAM_STAGE_TIMING = 3
 SM_PARAM_SGM_P1 = 4
 SM_PARAM_SGM_P2 = 5
+SM_PARAM_BOX_KERNEL = 6
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (

@@ -647,8 +647,19 @@ int mid_tiles_max() {
     return v;
 }
 
+// SM_BOX_MFMA=0 (read once) keeps the VALU kernels for every launch in auto mode (A/B timing)
+bool box_mfma_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("SM_BOX_MFMA");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
+// box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the kernels of this file, 2 the matrix-pipe kernel
+// (bm_box_mfma.hip) at any launch size; outside that kernel's scope (the right view, r = 0, r > 7) 2 is 0
 template <int R, int DMAX, bool RIGHT>
-hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s) {
+hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel) {
     using G = Geo<R, DMAX, kWavesD<RIGHT, R, DMAX>>;
     const int tiles_x = (a.W + G::TW - 1) / G::TW;
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
@@ -671,6 +682,8 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         // one tile per CU the 4-wave kernel wins: with one 16-wave workgroup per CU a tile's staging
         // overlaps no other tile's compute (1080p batch 1: 102.8 vs 87.8 us).
         const int npairs = ((a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1)) / 2;
+        const bool mfma_ok = R >= 1 && R <= kMaxFastRadius && box_mfma_scope(a);
+        if (mfma_ok && box_kernel == 2) return launch_box_match_mfma(a, batch, s);
         if constexpr (!kWideR<R>) {
             if (wide_tiles_enabled() && blocks <= compute_units() && npairs >= 2 * kWideTile) {
                 using GW = Geo<R, DMAX, kWideTile>;
@@ -687,6 +700,13 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
                 return hipGetLastError();
             }
         }
+        // launches past the 8-wave tiles' range (a batch of frames: the throughput path) take the matrix-pipe
+        // kernel: 1080p D = 128 r = 5, 128 frames per launch, 6.91 -> 6.04 ms; D = 256 x 32 frames 3.51 -> 2.94;
+        // 4K D = 192 x 8 frames 2.51 -> 2.10; batch 1 stays on the 8-wave tiles (0.070 against 0.071 ms)
+        // (profiles/microbench/box_mfma_headline_ab.txt)
+        if (mfma_ok && box_kernel == 0 && box_mfma_enabled() &&
+            blocks > (int64_t)(mid_tiles_max() > 0 ? mid_tiles_max() : 8) * compute_units())
+            return launch_box_match_mfma(a, batch, s);
         hipLaunchKernelGGL((box_match_kernel<R, DMAX, false>), dim3((unsigned)blocks), dim3(64 * kWaves<false, R>),
                            (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
     }
@@ -694,14 +714,14 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
 }
 
 template <int R, bool RIGHT>
-hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s) {
+hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel = 0) {
     const int dspan = (a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1);
-    if (dspan <= 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s);
-    if (dspan <= 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s);
+    if (dspan <= 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel);
+    if (dspan <= 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel);
     // 192 (cfg5): the right band and the right-key rows sized for 192, not 256, keep the plain kernel
     // at 4 workgroups/CU and the right-view kernel at 2
-    if (dspan <= 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s);
-    return launch_rd<R, 256, RIGHT>(a, batch, ro, s);
+    if (dspan <= 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel);
+    return launch_rd<R, 256, RIGHT>(a, batch, ro, s, box_kernel);
 }
 
 template <int R>
@@ -756,24 +776,24 @@ __global__ __launch_bounds__(256) void box_match_generic_kernel(MatchArgs a, int
 
 }  // namespace
 
-hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s) {
+hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel) {
     switch (a.radius) {
-        case 0: return launch_r<0, false>(a, batch, nullptr, s);
-        case 1: return launch_r<1, false>(a, batch, nullptr, s);
-        case 2: return launch_r<2, false>(a, batch, nullptr, s);
-        case 3: return launch_r<3, false>(a, batch, nullptr, s);
-        case 4: return launch_r<4, false>(a, batch, nullptr, s);
-        case 5: return launch_r<5, false>(a, batch, nullptr, s);
-        case 6: return launch_r<6, false>(a, batch, nullptr, s);
-        case 7: return launch_r<7, false>(a, batch, nullptr, s);
-        case 8: return launch_r<8, false>(a, batch, nullptr, s);
-        case 9: return launch_r<9, false>(a, batch, nullptr, s);
-        case 10: return launch_r<10, false>(a, batch, nullptr, s);
-        case 11: return launch_r<11, false>(a, batch, nullptr, s);
-        case 12: return launch_r<12, false>(a, batch, nullptr, s);
-        case 13: return launch_r<13, false>(a, batch, nullptr, s);
-        case 14: return launch_r<14, false>(a, batch, nullptr, s);
-        case 15: return launch_r<15, false>(a, batch, nullptr, s);
+        case 0: return launch_r<0, false>(a, batch, nullptr, s, box_kernel);
+        case 1: return launch_r<1, false>(a, batch, nullptr, s, box_kernel);
+        case 2: return launch_r<2, false>(a, batch, nullptr, s, box_kernel);
+        case 3: return launch_r<3, false>(a, batch, nullptr, s, box_kernel);
+        case 4: return launch_r<4, false>(a, batch, nullptr, s, box_kernel);
+        case 5: return launch_r<5, false>(a, batch, nullptr, s, box_kernel);
+        case 6: return launch_r<6, false>(a, batch, nullptr, s, box_kernel);
+        case 7: return launch_r<7, false>(a, batch, nullptr, s, box_kernel);
+        case 8: return launch_r<8, false>(a, batch, nullptr, s, box_kernel);
+        case 9: return launch_r<9, false>(a, batch, nullptr, s, box_kernel);
+        case 10: return launch_r<10, false>(a, batch, nullptr, s, box_kernel);
+        case 11: return launch_r<11, false>(a, batch, nullptr, s, box_kernel);
+        case 12: return launch_r<12, false>(a, batch, nullptr, s, box_kernel);
+        case 13: return launch_r<13, false>(a, batch, nullptr, s, box_kernel);
+        case 14: return launch_r<14, false>(a, batch, nullptr, s, box_kernel);
+        case 15: return launch_r<15, false>(a, batch, nullptr, s, box_kernel);
         default: return launch_box_match_generic(a, batch, s);
     }
 }

@@ -1,0 +1,363 @@
+// bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices.
+//
+// Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
+//
+// Tile: 64 x 64 input pixels from (x0 - R, y0 - R) -> TO x TO outputs, TO = 64 - 2R.  Four waves split the
+// tile's d range; each keeps its best keys for the whole tile in registers (64 VGPRs) in the accumulator
+// layout, folded once at the end through LDS.
+//
+// Exactness: every number is an integer its format holds exactly.
+//   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
+//             clearing the sign bits gives AD in 0..255.  Rows outside the image stage 0 on both sides (AD 0);
+//             columns with c < d or c >= W get AD = 0 by one select per AD register, in the tiles that have any.
+//   stage 1   (vertical, M = 16 image columns, K = 32 input rows, N = 16 output rows)
+//             D1 = sum AD - BIAS, BIAS = ceil((2R+1) * 255 / 2) in the C operand: |D1| <= 1913 < 2048 at R = 7,
+//             so v_cvt_pk to f16 is exact.
+//   stage 2   (horizontal, M = 16 output columns, K = 32 input columns, N = 16 output rows), band value 256,
+//             C = 256 * (2R+1) * BIAS + d: the f32 accumulator is the key (S << 8 | d) < 2^24, and every partial
+//             sum stays an integer below 2^24 in magnitude, so the accumulation order does not matter.
+//   WTA       positive f32 bit patterns order like unsigned integers: min on the raw bits, ties to the smaller
+//             d as in Device.cu:57; one v_cvt_u32_f32 per output pixel in the epilogue, then the seed.
+//
+// Operand layout (lane l, g = l >> 4): A holds row l & 15, k = 8g..8g+7; B holds column l & 15, k = 8g..8g+7;
+// C/D hold column l & 15, rows 4g..4g+3.  Stage 1's D (output row l & 15, image columns 4g..4g+3 of a
+// 16-column block) packed to f16 is half of a stage-2 B operand; two adjacent column blocks make its K = 32 in
+// the order (4g + j, 16 + 4g + j), and the constant horizontal band (the A operand) is built in that order.
+// R sits in LDS column-major ([column][64 rows] f16, 128 B per column, 16-B row groups XOR-swizzled by the
+// column), so a lane's R operand for any d is one ds_read_b128 at column x - d.
+#include <type_traits>
+
+#include "bm_common.h"
+
+namespace sm {
+namespace {
+
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+
+constexpr int kT = 64;          // input tile edge
+constexpr int kNW = 4;          // waves per workgroup, one per SIMD
+constexpr int kThreads = 64 * kNW;
+constexpr int kColB = 128;      // bytes per staged column (64 rows of f16)
+constexpr int kFoldStride = 65; // dwords per row of the fold plane
+constexpr uint32_t kInfBits = 0x7F800000u;
+
+template <int R, int DMAX>
+struct MG {
+    static constexpr int TO = kT - 2 * R;               // outputs per tile, each way
+    static constexpr int RC = kT + DMAX;                // staged right-band columns
+    static constexpr int RS_BYTES = RC * kColB;
+    static constexpr int L_BYTES = kT * kColB;
+    static constexpr int LDS_BYTES = RS_BYTES + L_BYTES;
+    static constexpr int BIAS = ((2 * R + 1) * 255 + 1) / 2;
+    static_assert(kT * kFoldStride * 4 <= LDS_BYTES, "the fold plane aliases the staged tiles");
+    static_assert(BIAS < 2048 && (2 * R + 1) * 255 - BIAS < 2048, "D1 exact in f16");
+    static_assert((int64_t)(2 * R + 1) * (2 * R + 1) * 255 * 256 + 255 < (1 << 24), "keys exact in f32");
+};
+
+// byte offset of 16-B row group q (rows 8q..8q+7) of staged column `col`
+__device__ __forceinline__ int slot(int col, int q) { return col * kColB + ((q ^ ((col >> 1) & 7)) << 4); }
+
+// 4 image bytes of row y from column x (little-endian), bytes outside the image read as 0
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p, int y, int x, int W, int H, int pitch) {
+    if (y < 0 || y >= H) return 0u;
+    const uint8_t* row = p + (int64_t)y * pitch;
+    if (x >= 0 && x + 3 < W) {
+        uint32_t v;
+        __builtin_memcpy(&v, row + x, 4);
+        return v;
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
+    return v;
+}
+
+// stage 4 * NC4 columns x 64 rows of `img` from (ytop, xleft) as f16 1024 + v, column-major
+template <int NC4>
+__device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xleft, int W, int H, int pitch,
+                                           uint8_t* dst, int tid) {
+    for (int e = tid; e < 8 * NC4; e += kThreads) {
+        const int q = e / NC4, j = e - q * NC4;
+        uint32_t w[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = ld_u32(img, ytop + 8 * q + i, xleft + 4 * j, W, H, pitch);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            u4 v;
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+                v[m] = 0x64006400u | ((w[2 * m] >> (8 * b)) & 0xFFu) | (((w[2 * m + 1] >> (8 * b)) & 0xFFu) << 16);
+            *reinterpret_cast<u4*>(dst + slot(4 * j + b, q)) = v;
+        }
+    }
+}
+
+__device__ __forceinline__ u4 abs_diff(u4 l, u4 r) {
+    u4 ad;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {   // v_pk_add_f16 with neg on r, then the two sign bits
+        const uint32_t lm = l[m], rm = r[m];
+        const h2 d = __builtin_bit_cast(h2, lm) - __builtin_bit_cast(h2, rm);
+        ad[m] = __builtin_bit_cast(uint32_t, d) & 0x7FFF7FFFu;
+    }
+    return ad;
+}
+
+__device__ __forceinline__ uint2 pack_f16(f4 v) {
+    uint2 p;
+    p.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(v[0], v[1]));   // exact: integers below 2048
+    p.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(v[2], v[3]));
+    return p;
+}
+
+__device__ __forceinline__ f4 mfma(u4 a, u4 b, f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
+}
+
+template <int R, int DMAX>
+__global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int tiles_x, int tiles_y) {
+    using G = MG<R, DMAX>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t* rsm = smem;                  // [RC][64] f16, swizzled
+    uint8_t* lsm = smem + G::RS_BYTES;    // [64][64] f16, swizzled
+
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int l16 = lane & 15;
+    const int g = lane >> 4;
+
+    const int tiles = tiles_x * tiles_y;
+    const int tile_id = xcd_tile(blockIdx.x, gridDim.x);   // [frame][ty][tx]
+    const int frame = tile_id / tiles;
+    const int t = tile_id - frame * tiles;
+    const int ty = t / tiles_x;
+    const int tx = t - ty * tiles_x;
+    const int x0 = tx * G::TO;
+    const int y0 = ty * G::TO;
+    const int W = a.W, H = a.H;
+    const int d_lo = a.d_lo, d_hi = a.d_hi;
+
+    const uint8_t* Lf = a.left + (int64_t)frame * a.frame_stride;
+    const uint8_t* Rf = a.right + (int64_t)frame * a.frame_stride;
+
+    // staged right column k is image column band0 + k: pixel column c at disparity d reads k = c - d - band0
+    const int band0 = x0 - R - d_lo - DMAX;
+    stage_cols<G::RC / 4>(Rf, y0 - R, band0, W, H, a.pitch, rsm, tid);
+    stage_cols<kT / 4>(Lf, y0 - R, x0 - R, W, H, a.pitch, lsm, tid);
+
+    // ---- constant bands ----
+    // vertical (B operand of stage 1): element j is input row k = 8g + j of a 32-row chunk against output row
+    // n = l16 of a 16-row block; the chunk starts `off` rows past the block: 1.0 where 0 <= off + k - n <= 2R
+    u4 bv0, bvm, bvp;   // off = 0, -16, +16
+    // horizontal (A operand of stage 2): 256.0 where 0 <= xin - l16 <= 2R; K = two 16-column blocks, elements
+    // 0..3 of a lane the columns 4g.. of one and 4..7 of the other: bh with the left block first, bhs swapped
+    u4 bh, bhs;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        uint32_t w0 = 0, wm = 0, wp = 0, wh = 0, ws = 0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = 2 * m + e;
+            const int dv = 8 * g + j - l16;
+            const int xin = j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4);
+            const int dh = xin - l16;
+            const int ds = (j < 4 ? 16 + 4 * g + j : 4 * g + (j - 4)) - l16;
+            w0 |= (dv >= 0 && dv <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            wm |= (dv - 16 >= 0 && dv - 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            wp |= (dv + 16 >= 0 && dv + 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            wh |= (dh >= 0 && dh <= 2 * R ? 0x5C00u : 0u) << (16 * e);
+            ws |= (ds >= 0 && ds <= 2 * R ? 0x5C00u : 0u) << (16 * e);
+        }
+        bv0[m] = w0;
+        bvm[m] = wm;
+        bvp[m] = wp;
+        bh[m] = wh;
+        bhs[m] = ws;
+    }
+    const float nbias = -(float)G::BIAS;
+    const f4 c1 = {nbias, nbias, nbias, nbias};
+    const float c2base = (float)(256 * (2 * R + 1) * G::BIAS);
+
+    // best keys as f32 bit patterns: [output row block][output column block][column 4g + i], row l16
+    uint32_t best[4][4][4];
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+        for (int xb = 0; xb < 4; ++xb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) best[ob][xb][i] = kInfBits;
+
+    // disparities past W - x0 are invalid for every output of the tile (Device.cu:44's break)
+    const int d_end = min(d_hi, W - x0 + 1);
+    const int nd = max(d_end - d_lo, 0);
+    const int dw_lo = d_lo + (wave * nd) / kNW;
+    const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
+    // largest d valid for every output of the tile
+    const int d_free = W - (min(x0 + G::TO, W) - 1);
+    // tiles with a column left of some d, a column past the image, or a partly valid d take the masked loop
+    const bool masked_tile = (x0 - R < d_hi) || (x0 - R + kT > W) || (d_end - 1 > d_free);
+
+    const int laddr = slot(l16, g);   // + 16 columns per block; chunk 1 is ^ 64
+
+    __syncthreads();
+
+    auto run = [&](auto masked_c) {
+        constexpr bool MASKED = decltype(masked_c)::value;
+        for (int d = dw_lo; d < dw_hi; ++d) {
+            const int k0 = l16 + DMAX + d_lo - d;
+            const int raddr = slot(k0, g);
+            // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the d-dependent
+            // zero (d >= 0) keeps the reads inside the loop
+            const int laddr_d = laddr + (int)((uint32_t)d >> 31);
+            const float c2v = c2base + (float)d;
+            const f4 c2 = {c2v, c2v, c2v, c2v};
+            const bool dm = MASKED && d > d_free;
+            // t[ob]: the packed D1 of two adjacent column blocks, a stage-2 B operand.  Even blocks go to its low
+            // half and odd blocks to its high half, so no half is ever copied; bh or bhs matches the order.  The
+            // last output block (cb == 4) pairs block 3 with the stale block 2: with the left block in the high
+            // half the stale columns meet only outputs past TO, which are never written
+            u4 t[4];
+#pragma unroll
+            for (int cb = 0; cb <= 4; ++cb) {
+                if (cb < 4) {
+                    const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr + cb * 16 * kColB);
+                    const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr ^ 64) + cb * 16 * kColB);
+                    const u4 l0 = *reinterpret_cast<const u4*>(lsm + laddr_d + cb * 16 * kColB);
+                    const u4 l1 = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ 64) + cb * 16 * kColB);
+                    u4 ad0 = abs_diff(l0, r0);
+                    u4 ad1 = abs_diff(l1, r1);
+                    if constexpr (MASKED) {
+                        const int c = x0 - R + 16 * cb + l16;
+                        const bool ok = c >= d && c < W;
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) {
+                            ad0[m] = ok ? ad0[m] : 0u;
+                            ad1[m] = ok ? ad1[m] : 0u;
+                        }
+                    }
+                    // output row blocks 0..3 of this column block from the two 32-row chunks
+                    f4 s0 = mfma(ad0, bv0, c1);
+                    f4 s1 = mfma(ad0, bvm, c1);
+                    s1 = mfma(ad1, bvp, s1);
+                    f4 s2 = mfma(ad1, bv0, c1);
+                    f4 s3 = mfma(ad1, bvm, c1);
+                    const f4 sv[4] = {s0, s1, s2, s3};
+#pragma unroll
+                    for (int ob = 0; ob < 4; ++ob) {
+                        const uint2 p = pack_f16(sv[ob]);
+                        t[ob][2 * (cb & 1)] = p.x;
+                        t[ob][2 * (cb & 1) + 1] = p.y;
+                    }
+                }
+                if (cb >= 1) {
+                    const int xb = cb - 1;
+#pragma unroll
+                    for (int ob = 0; ob < 4; ++ob) {
+                        const u4 o = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[ob], c2));
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            uint32_t k = o[i];
+                            if constexpr (MASKED) {
+                                if (dm) k = (d <= W - (x0 + 16 * xb + 4 * g + i)) ? k : kInfBits;
+                            }
+                            best[ob][xb][i] = min(best[ob][xb][i], k);
+                        }
+                    }
+                }
+            }
+        }
+    };
+    if (masked_tile) run(std::true_type{});
+    else run(std::false_type{});
+
+    __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
+
+    // ---- fold the waves (same lane = same pixels in every wave) through one LDS plane ----
+    uint32_t* fold = reinterpret_cast<uint32_t*>(smem);   // [64][kFoldStride] f32 bit patterns
+    if (wave == 0) {
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+            for (int xb = 0; xb < 4; ++xb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    fold[(16 * ob + l16) * kFoldStride + 16 * xb + 4 * g + i] = best[ob][xb][i];
+    }
+    __syncthreads();
+    if (wave != 0) {
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+            for (int xb = 0; xb < 4; ++xb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    atomicMin(&fold[(16 * ob + l16) * kFoldStride + 16 * xb + 4 * g + i], best[ob][xb][i]);
+    }
+    __syncthreads();
+    uint8_t* Df = a.disp ? a.disp + (int64_t)frame * a.out_frame_stride : nullptr;
+    uint32_t* Kf = a.keys ? a.keys + (int64_t)frame * W * H : nullptr;
+    // lane = output column, rows over the waves
+    if (lane < G::TO && x0 + lane < W) {
+        const int ylim = min(G::TO, H - y0);
+        uint8_t* drow = Df ? Df + (int64_t)y0 * a.out_pitch + x0 + lane : nullptr;
+        uint32_t* krow = Kf ? Kf + (int64_t)y0 * W + x0 + lane : nullptr;
+        for (int j = wave; j < ylim; j += kNW) {
+            // the f32 key to its integer (+inf: no valid d), then the seed
+            const uint32_t kb = fold[j * kFoldStride + lane];
+            const uint32_t kf = kb >= kInfBits ? 0xFFFFFFFFu : (uint32_t)__builtin_bit_cast(float, kb);
+            const uint32_t k = min(kf, a.seed_key);
+            if (drow) drow[(int64_t)j * a.out_pitch] = k < a.thresh_key ? (uint8_t)(k & 0xFFu) : (uint8_t)0;
+            if (krow) krow[(int64_t)j * W] = k;
+        }
+    }
+}
+
+template <int R, int DMAX>
+hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s) {
+    using G = MG<R, DMAX>;
+    const int tiles_x = (a.W + G::TO - 1) / G::TO;
+    const int tiles_y = (a.H + G::TO - 1) / G::TO;
+    const int64_t blocks = (int64_t)tiles_x * tiles_y * batch;
+    if (blocks <= 0 || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((box_mfma_kernel<R, DMAX>), dim3((unsigned)blocks), dim3(kThreads), (size_t)G::LDS_BYTES, s, a,
+                       tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+template <int R>
+hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s) {
+    const int dspan = a.d_hi - a.d_lo;
+    if (dspan <= 64) return launch_rd<R, 64>(a, batch, s);
+    if (dspan <= 128) return launch_rd<R, 128>(a, batch, s);
+    if (dspan <= 192) return launch_rd<R, 192>(a, batch, s);
+    return launch_rd<R, 256>(a, batch, s);
+}
+
+}  // namespace
+
+bool box_mfma_scope(const MatchArgs& a) {
+    return a.radius >= 1 && a.radius <= kMaxFastRadius && a.valid_mode == 0 && a.d_lo >= 0 && a.d_hi > a.d_lo &&
+           a.d_hi <= kMaxDisp;
+}
+
+hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s) {
+    if (!box_mfma_scope(a)) return hipErrorInvalidValue;
+    switch (a.radius) {
+        case 1: return launch_r<1>(a, batch, s);
+        case 2: return launch_r<2>(a, batch, s);
+        case 3: return launch_r<3>(a, batch, s);
+        case 4: return launch_r<4>(a, batch, s);
+        case 5: return launch_r<5>(a, batch, s);
+        case 6: return launch_r<6>(a, batch, s);
+        case 7: return launch_r<7>(a, batch, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace sm

@@ -63,6 +63,7 @@ struct sm_handle {
     // host calls record the upload / match / download split (SM_PARAM_STAGE_TIMING): 0 off, 1 on, 2 auto
     // (default: on once sm_last_stage_ms has been called on the handle, or when SM_VERBOSE is set)
     int stage_timing = 2;
+    int box_kernel = 0;          // SM_PARAM_BOX_KERNEL: 0 auto, 1 VALU kernels, 2 matrix-pipe kernel
     bool stage_requested = false;
     // The workspaces above are shared by every call on the handle while calls run on the stream
     // they are given: the end of each pass is recorded here, and a pass on another stream waits
@@ -536,7 +537,7 @@ int run_device_body(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int
         // mirrored right view below takes it too)
         SM_HIP(sm::launch_box_match_strip(a, batch, s));
     } else {
-        SM_HIP(sm::launch_box_match(a, batch, s));
+        SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel));
     }
     if (med) SM_HIP(sm::launch_median(left_raw, W, H, W, P, batch, kMedianRadius, disp, opitch, ostride, s));
     if (!lr) return SM_OK;
@@ -994,7 +995,7 @@ int slice_keys_pass(sm_handle* h, const uint8_t* dL, const uint8_t* dR, int W, i
             SM_HIP(sm::launch_box_match_wide(a, 1, reinterpret_cast<uint16_t*>(h->d_vol), nullptr, 0, 0, s));
             return SM_OK;
         }
-        SM_HIP(sm::launch_box_match(a, 1, s));
+        SM_HIP(sm::launch_box_match(a, 1, s, h->box_kernel));
         return SM_OK;
     }
     if (sm::wide_path(radius, W, H, pitch)) {   // r 16..127: the wide path's right row, keys sign-flipped
@@ -1359,6 +1360,12 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         if (!(value >= 0.f) || value > 65535.f || (float)v != value)
             return fail(SM_ERR_INVALID_ARG, "SGM penalty must be an integer in [0, 65535] (0 = auto)");
         (param == SM_PARAM_SGM_P1 ? h->sgm_p1 : h->sgm_p2) = v;
+        return SM_OK;
+    }
+    if (param == SM_PARAM_BOX_KERNEL) {
+        if (value != 0.f && value != 1.f && value != 2.f)
+            return fail(SM_ERR_INVALID_ARG, "box kernel is 0 (auto), 1 (legacy) or 2 (matrix)");
+        h->box_kernel = (int)value;
         return SM_OK;
     }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);

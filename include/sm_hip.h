@@ -127,9 +127,15 @@ enum {
                                   Setting 2 again returns to the unarmed default */
     SM_PARAM_SGM_P1 = 4,       /* SM_AGG_SGM penalty of a disparity step of 1: an integer >= 0, 0 (default) =
                                   auto, 8 * win^2 */
-    SM_PARAM_SGM_P2 = 5        /* SM_AGG_SGM penalty of a larger step: an integer >= 0, 0 (default) = auto,
+    SM_PARAM_SGM_P2 = 5,       /* SM_AGG_SGM penalty of a larger step: an integer >= 0, 0 (default) = auto,
                                   32 * win^2.  P1 <= P2 and 255 * win^2 + P2 <= 65535 are checked by the matching
                                   call, against its radius (sm_sgm_check) */
+    SM_PARAM_BOX_KERNEL = 6    /* which kernel the plain box pass (no LR, no median workspace needed) runs: 0
+                                  (default) auto by launch size, 1 the VALU kernels at every size, 2 the
+                                  matrix-pipe kernel at every size.  The maps and keys are the same bit for bit.
+                                  The matrix-pipe kernel covers radius 1..7 without the fused right view: with
+                                  SM_LR_CHECK, radius 0 or radius >= 8 the value 2 silently runs the VALU
+                                  kernels.  Other values: SM_ERR_INVALID_ARG */
 };
 
 typedef struct sm_handle sm_handle;
