@@ -29,7 +29,7 @@ from .gray import bgr_to_gray  # noqa: F401
 __all__ = [
     "BlockMatcher", "BlockMatcherGroup", "blockMatching_gpu", "block_matching_gpu", "SMError", "synth_pair", "bgr_to_gray",
     "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_COST_CENSUS", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
-    "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes",
+    "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes", "to_float",
 ]
 
 DEFAULT_GUIDED_EPS = 1e-4 * 255.0 * 255.0
@@ -88,6 +88,15 @@ def census_workspace_bytes(width: int, height: int, num_disp: int, radius: int, 
     _capi.check(_capi.load().sm_census_workspace_bytes(width, height, num_disp, radius, _flags(agg, False, False, "census"),
                                                        ctypes.byref(n)))
     return n.value
+
+
+def to_float(disp16):
+    """A 1/16-px map (numpy uint16, or a torch int16 tensor holding the same bit patterns) as float32 pixels:
+    q / 16, 0 where the pixel is invalid."""
+    if isinstance(disp16, np.ndarray):
+        return disp16.astype(np.float32) * np.float32(0.0625)
+    import torch
+    return disp16.to(torch.float32) * 0.0625
 
 
 def _check_out(out_t, shape, dtype, device, name: str = "out_t"):
@@ -529,6 +538,120 @@ class BlockMatcher:
         _capi.check(self._lib.sm_match_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, W, B, H * W,
                                               radius, num_disp, _flags(agg, lr_check, median, cost), out_t.data_ptr(), W,
                                               H * W, self._stream_ptr(stream)))
+        return out_t
+
+    # -- sub-pixel maps (1/16 px, uint16), uniqueness filter, reprojection ------------------
+    def set_uniqueness(self, u: int = 0):
+        """Uniqueness ratio of the sub-pixel calls (SM_PARAM_UNIQUENESS): an integer 0..99, 0 = off.  A pixel is
+        invalid when a disparity more than 1 away from its best costs less than best * 100 / (100 - u)."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_UNIQUENESS, float(u)))
+
+    def match_subpix(self, left, right, radius: int, num_disp: int, agg: str = "sgm", cost: str = "ad",
+                     lr_check: bool = False, return_right: bool = False, return_mask: bool = False):
+        """uint16 [H, W] disparity in 1/16 px (sm_block_match_subpix_u16): 16 * d + a parabola fit through the
+        costs next to the best d, 0 where the pixel is invalid (uniqueness, the AD box threshold) or occluded
+        (lr_check).  agg 'box' or 'sgm', cost 'ad' or 'census', radius <= 7.  return_right / return_mask: a tuple
+        (map[, right-view map][, uint8 valid mask])."""
+        L = _as_u8_image(left, "left")
+        R = _as_u8_image(right, "right")
+        if L.shape != R.shape:
+            raise ValueError("left/right sizes differ")
+        H, W = L.shape
+        out = np.empty((H, W), np.uint16)
+        rd = np.empty((H, W), np.uint16) if return_right else None
+        mask = np.empty((H, W), np.uint8) if return_mask else None
+        _capi.check(self._lib.sm_block_match_subpix_u16(
+            self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp, _flags(agg, lr_check, False, cost),
+            out.ctypes.data, rd.ctypes.data if return_right else None, mask.ctypes.data if return_mask else None, W))
+        res = (out,) + ((rd,) if return_right else ()) + ((mask,) if return_mask else ())
+        return res[0] if len(res) == 1 else res
+
+    def match_subpix_device(self, left_t, right_t, radius: int, num_disp: int, out_t=None, agg: str = "sgm",
+                            cost: str = "ad", lr_check: bool = False, right_t16=None, mask_t=None, stream=None):
+        """Device form of :meth:`match_subpix` (sm_match_subpix_device), async on `stream`.  left_t / right_t: uint8
+        cuda tensors [H, W] or [B, H, W] of one layout whose rows are contiguous (row and frame strides are passed
+        on).  The map comes back as an int16 tensor holding the uint16 bit patterns (at most 4088, so the values
+        read the same); out_t may be any int16 tensor of the frames' shape with contiguous rows.  right_t16 (int16)
+        and mask_t (uint8): optional contiguous tensors of the frames' shape for the right-view map and the mask."""
+        import torch
+        if left_t.dtype != torch.uint8 or right_t.dtype != torch.uint8:
+            raise ValueError("expected uint8 tensors")
+        if left_t.shape != right_t.shape or left_t.dim() not in (2, 3) or left_t.stride() != right_t.stride():
+            raise ValueError("left/right must be equal [H,W] or [B,H,W] tensors of one layout")
+        if not (left_t.is_cuda and right_t.is_cuda) or left_t.stride(-1) != 1:
+            raise ValueError("expected device tensors with contiguous rows")
+        if left_t.device != right_t.device or left_t.device.index != self.device:
+            raise ValueError(f"frames must be on cuda:{self.device}, the handle's device")
+        B = 1 if left_t.dim() == 2 else left_t.shape[0]
+        H, W = left_t.shape[-2:]
+        if out_t is None:
+            out_t = torch.empty(tuple(left_t.shape), dtype=torch.int16, device=left_t.device)
+        if out_t.dtype != torch.int16 or out_t.shape != left_t.shape or out_t.stride(-1) != 1 \
+                or out_t.device != left_t.device:
+            raise ValueError("out_t must be an int16 tensor of the frames' shape with contiguous rows")
+        if right_t16 is not None:
+            _check_out(right_t16, left_t.shape, torch.int16, left_t.device, "right_t16")
+        if mask_t is not None:
+            _check_out(mask_t, left_t.shape, torch.uint8, left_t.device, "mask_t")
+        fs = left_t.stride(0) if left_t.dim() == 3 else left_t.stride(-2) * H
+        ofs = out_t.stride(0) if out_t.dim() == 3 else out_t.stride(-2) * H
+        _capi.check(self._lib.sm_match_subpix_device(
+            self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, left_t.stride(-2), B, fs, radius, num_disp,
+            _flags(agg, lr_check, False, cost), out_t.data_ptr(), out_t.stride(-2), ofs,
+            right_t16.data_ptr() if right_t16 is not None else None,
+            mask_t.data_ptr() if mask_t is not None else None, self._stream_ptr(stream)))
+        return out_t
+
+    def volume_wta_subpix_device(self, vol_t, invalid_from: int = 0, lr_check: bool = False, out_t=None,
+                                 right_t16=None, mask_t=None, stream=None):
+        """The sub-pixel WTA on a caller's cost volume (sm_volume_wta_subpix_device): vol_t a contiguous
+        [D, H, W] cuda tensor of int16 (uint16 bit patterns) or int32 (uint32, costs < 2^24); the left view is
+        invalid where its best cost is >= invalid_from (0 = no threshold); the handle's uniqueness applies.
+        Returns the int16 [H, W] map (uint16 bit patterns)."""
+        import torch
+        if vol_t.dtype not in (torch.int16, torch.int32) or vol_t.dim() != 3 or not vol_t.is_cuda \
+                or not vol_t.is_contiguous():
+            raise ValueError("vol_t must be a contiguous int16 or int32 [D, H, W] device tensor")
+        D, H, W = vol_t.shape
+        if out_t is None:
+            out_t = torch.empty((H, W), dtype=torch.int16, device=vol_t.device)
+        _check_out(out_t, (H, W), torch.int16, vol_t.device)
+        if right_t16 is not None:
+            _check_out(right_t16, (H, W), torch.int16, vol_t.device, "right_t16")
+        if mask_t is not None:
+            _check_out(mask_t, (H, W), torch.uint8, vol_t.device, "mask_t")
+        _capi.check(self._lib.sm_volume_wta_subpix_device(
+            self._h, vol_t.data_ptr(), vol_t.element_size(), W, H, D, int(invalid_from),
+            SM_LR_CHECK if lr_check else 0, out_t.data_ptr(), W,
+            right_t16.data_ptr() if right_t16 is not None else None,
+            mask_t.data_ptr() if mask_t is not None else None, self._stream_ptr(stream)))
+        return out_t
+
+    def reproject(self, disp16, Q) -> np.ndarray:
+        """reprojectImageTo3D of a 1/16-px uint16 map (sm_reproject_u16): float32 [H, W, 3] points (X, Y, Z) / w of
+        Q (x, y, q / 16, 1), (0, 0, 0) where q == 0.  Q: the 4 x 4 matrix of ``calib.stereo_rectify``."""
+        d = np.ascontiguousarray(disp16)
+        if d.dtype != np.uint16 or d.ndim != 2:
+            raise ValueError(f"disp16: expected a 2-D uint16 map, got {d.dtype} {d.shape}")
+        Q = np.ascontiguousarray(Q, np.float64).reshape(16)
+        H, W = d.shape
+        out = np.empty((H, W, 3), np.float32)
+        _capi.check(self._lib.sm_reproject_u16(self._h, d.ctypes.data, W, H, W, Q.ctypes.data, out.ctypes.data, 3 * W))
+        return out
+
+    def reproject_device(self, disp_t16, Q, out_t=None, stream=None):
+        """Device form of :meth:`reproject`: disp_t16 an int16 [H, W] cuda tensor with contiguous rows (uint16 bit
+        patterns, as match_subpix_device returns), the points a float32 [H, W, 3] tensor; async on `stream`."""
+        import torch
+        if disp_t16.dtype != torch.int16 or disp_t16.dim() != 2 or not disp_t16.is_cuda or disp_t16.stride(-1) != 1:
+            raise ValueError("disp_t16 must be an int16 [H, W] device tensor with contiguous rows")
+        Q = np.ascontiguousarray(Q, np.float64).reshape(16)
+        H, W = disp_t16.shape
+        if out_t is None:
+            out_t = torch.empty((H, W, 3), dtype=torch.float32, device=disp_t16.device)
+        _check_out(out_t, (H, W, 3), torch.float32, disp_t16.device)
+        _capi.check(self._lib.sm_reproject_device(self._h, disp_t16.data_ptr(), W, H, disp_t16.stride(0),
+                                                  Q.ctypes.data, out_t.data_ptr(), 3 * W, self._stream_ptr(stream)))
         return out_t
 
     def slice_keys_device(self, left_t, right_t, radius: int, d_lo: int, d_hi: int, keys_t=None, stream=None):

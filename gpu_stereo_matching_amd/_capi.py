@@ -33,6 +33,7 @@ SM_PARAM_STAGE_TIMING = 3
 SM_PARAM_SGM_P1 = 4
 SM_PARAM_SGM_P2 = 5
 SM_PARAM_BOX_KERNEL = 6
+SM_PARAM_UNIQUENESS = 7
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (
@@ -51,6 +52,8 @@ EXPORTED = (
     "sm_dslice_plan", "sm_dslice_rehearse_u8", "sm_slice_keys_lr_device", "sm_right_keys_to_disp_device",
     "sm_lr_check_device", "sm_sgm_check", "sm_sgm_workspace_bytes", "sm_census_workspace_bytes", "sm_census_device",
     "sm_census_volume_device", "sm_census_volume_u8",
+    "sm_match_subpix_device", "sm_block_match_subpix_u16", "sm_volume_wta_subpix_device", "sm_reproject_device",
+    "sm_reproject_u16",
 )
 
 
@@ -140,6 +143,11 @@ def load(path: str = LIB_PATH):
     L.sm_census_device.argtypes = [vp, vp, i, i, i, vp, vp]
     L.sm_census_volume_device.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
     L.sm_census_volume_u8.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    L.sm_match_subpix_device.argtypes = [vp, vp, vp, i, i, i, i, i64, i, i, u, vp, i, i64, vp, vp, vp]
+    L.sm_block_match_subpix_u16.argtypes = [vp, vp, vp, i, i, i, i, i, u, vp, vp, vp, i]
+    L.sm_volume_wta_subpix_device.argtypes = [vp, vp, i, i, i, i, ctypes.c_uint32, u, vp, i, vp, vp, vp]
+    L.sm_reproject_device.argtypes = [vp, vp, i, i, i, vp, vp, i, vp]
+    L.sm_reproject_u16.argtypes = [vp, vp, i, i, i, vp, vp, i]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

@@ -138,6 +138,21 @@ hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp,
 // the same WTA, thresholdless, over a u16 cost volume [D][H][W] (SM_COST_CENSUS with SM_AGG_BOX)
 hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, uint8_t* disp, int out_pitch,
                                uint32_t* right_keys, hipStream_t s);
+// sub-pixel WTA (bm_subpix.hip) over a d-major volume [D][H][W] of costs < 2^24: disp16 [H][pitch] receives
+// q = 16 d0 + delta (1/16 px), right16 (optional, dense) the right view's q, mask (optional, dense) the validity.
+// invalid_from: 0, or the left view is invalid where its minimum is >= it; uniq 0..99: the uniqueness ratio (0 off);
+// right_pairs: 1 the right view over u + 2 d <= W, 2 over u + d < W; lr: the LR check on the two views' d0, through
+// `scratch` (2 W H bytes).  Invalid and occluded pixels get q = 0, mask = 0.
+hipError_t launch_subpix_wta_u32(const uint32_t* vol, int W, int H, int D, uint32_t invalid_from, int uniq,
+                                 int right_pairs, bool lr, uint16_t* disp16, int pitch, uint16_t* right16,
+                                 uint8_t* mask, uint8_t* scratch, hipStream_t s);
+hipError_t launch_subpix_wta_u16(const uint16_t* vol, int W, int H, int D, uint32_t invalid_from, int uniq,
+                                 int right_pairs, bool lr, uint16_t* disp16, int pitch, uint16_t* right16,
+                                 uint8_t* mask, uint8_t* scratch, hipStream_t s);
+// 1/16-px map -> points: xyz [H][xyz_pitch] floats, (X, Y, Z) / w of Q (x, y, q / 16, 1) (Q row-major 4 x 4),
+// (0, 0, 0) where q == 0 or w == 0
+hipError_t launch_reproject(const uint16_t* disp16, int W, int H, int pitch, const double* Q, float* xyz,
+                            int xyz_pitch, hipStream_t s);
 // census cost (bm_census.hip): the 9 x 7 census words u64 [H][W] of an image (replicated border, 62 bits), and
 // the Hamming volume u8 [D][H][W] of two census images, popcount(cL(y, x) ^ cR(y, x - d)) for x >= d, else 0:
 // the AD volume's layout, so launch_box_sad_volume sums it (<= 62 * win^2); W <= 4096

@@ -64,6 +64,7 @@ struct sm_handle {
     // (default: on once sm_last_stage_ms has been called on the handle, or when SM_VERBOSE is set)
     int stage_timing = 2;
     int box_kernel = 0;          // SM_PARAM_BOX_KERNEL: 0 auto, 1 VALU kernels, 2 matrix-pipe kernel
+    int uniqueness = 0;          // SM_PARAM_UNIQUENESS: 0 off, 1..99 the sub-pixel calls' uniqueness ratio
     bool stage_requested = false;
     // The workspaces above are shared by every call on the handle while calls run on the stream
     // they are given: the end of each pass is recorded here, and a pass on another stream waits
@@ -341,6 +342,89 @@ int cost_check(const sm_handle* h, int width, int radius, unsigned flags) {
     if (!(flags & SM_COST_CENSUS)) return SM_OK;
     if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, nullptr, nullptr);
     return census_check(width, radius, flags);
+}
+
+// ---- sub-pixel maps (bm_subpix.hip) ----
+// The argument rules of the sub-pixel matching calls, before the device is touched; the resolved SGM penalties
+// come back through p1_out / p2_out.
+int subpix_check(const sm_handle* h, int width, int height, int pitch, int radius, int num_disp, unsigned flags,
+                 int* p1_out, int* p2_out) {
+    // what the sub-pixel calls cannot do comes first and needs no handle; then the common argument checks
+    if (flags & SM_MEDIAN)
+        return fail(SM_ERR_INVALID_ARG,
+                    "sub-pixel: SM_MEDIAN is not supported (the ctmf median is an 8-bit histogram; there is no 16-bit "
+                    "median)");
+    if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
+        return fail(SM_ERR_INVALID_ARG,
+                    "sub-pixel: SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID keep no cost volume to interpolate "
+                    "(flags 0x%x)", flags);
+    if (radius > sm::kMaxFastRadius)
+        return fail(SM_ERR_INVALID_ARG, "sub-pixel: radius %d out of [0, %d] (the u16 cost volume)", radius,
+                    sm::kMaxFastRadius);
+    if (width > 4096) return fail(SM_ERR_INVALID_ARG, "sub-pixel: width %d out of [1, 4096]", width);
+    const int rc = check_geometry(h, width, height, pitch, radius, num_disp);
+    if (rc) return rc;
+    if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, p1_out, p2_out);
+    if (flags & SM_COST_CENSUS) return census_check(width, radius, flags);
+    return SM_OK;
+}
+
+// The 1/16-px maps of `batch` frames, one frame after another through the volume workspace, as run_sgm and
+// run_census_box: cost volume (AD or census, box-summed; SGM's sum over it) -> subpix_wta_kernel (-> LR check).
+// The two views' d0 of the check take the right-keys region.  right16 / mask: dense W x H planes or null.
+int run_subpix(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch, int64_t fstride,
+               int radius, int D, unsigned flags, int p1, int p2, uint16_t* disp16, int opitch, int64_t ostride,
+               uint16_t* right16, uint8_t* mask, hipStream_t s) {
+    const bool sgm = (flags & SM_AGG_SGM) != 0, census = (flags & SM_COST_CENSUS) != 0;
+    const bool lr = (flags & SM_LR_CHECK) != 0;
+    const int64_t P = (int64_t)W * H;
+    const CensusWs w = census_ws(P, D, sgm);   // the AD paths lay out [volume][costs][right keys] alike
+    const size_t bytes = census ? w.bytes : w.cl;
+    const int rc = ensure_vol(h, bytes);   // the only allocation of the pass, before any launch
+    if (rc)
+        return fail(rc, "sub-pixel: no %zu-byte workspace for %dx%d D=%d: %s", bytes, W, H, D,
+                    std::string(g_err).c_str());
+    uint32_t* S = reinterpret_cast<uint32_t*>(h->d_vol);
+    uint16_t* cost = reinterpret_cast<uint16_t*>(h->d_vol + w.sad);
+    uint8_t* scratch = h->d_vol + w.rkeys;
+    const uint32_t win = 2u * (uint32_t)radius + 1u;
+    const uint32_t invalid_from = sgm || census ? 0u : 50u * win * win;   // Device.cu:37, the AD box path alone
+    const int right_pairs = sgm || census ? 1 : 2;
+    for (int f = 0; f < batch; ++f) {
+        if (census) {
+            const int rcc = census_cost(L + f * fstride, R + f * fstride, W, H, pitch, D, h->d_vol, w, s);
+            if (rcc) return rcc;
+        } else {
+            SM_HIP(sm::launch_ad_volume(L + f * fstride, R + f * fstride, W, H, pitch, fstride, 1, D, h->d_vol, P * D,
+                                        s));
+        }
+        SM_HIP(sm::launch_box_sad_volume(h->d_vol, W, H, radius, D, cost, s));
+        uint16_t* out = disp16 + f * ostride;
+        uint16_t* rout = right16 ? right16 + f * P : nullptr;
+        uint8_t* mout = mask ? mask + f * P : nullptr;
+        if (sgm) {
+            SM_HIP(hipMemsetAsync(S, 0, (size_t)(4 * P * D), s));
+            SM_HIP(sm::launch_sgm_paths(cost, W, H, D, p1, p2, S, s));
+            SM_HIP(sm::launch_subpix_wta_u32(S, W, H, D, invalid_from, h->uniqueness, right_pairs, lr, out, opitch,
+                                             rout, mout, scratch, s));
+        } else {
+            SM_HIP(sm::launch_subpix_wta_u16(cost, W, H, D, invalid_from, h->uniqueness, right_pairs, lr, out, opitch,
+                                             rout, mout, scratch, s));
+        }
+    }
+    return SM_OK;
+}
+
+// the handle's workspaces are shared between streams: a pass is ordered after the last one (run_device)
+int scratch_wait(sm_handle* h, hipStream_t s) {
+    if (h->scratch_pending && h->scratch_stream != s) SM_HIP(hipStreamWaitEvent(s, h->scratch_ev, 0));
+    return SM_OK;
+}
+int scratch_record(sm_handle* h, hipStream_t s) {
+    SM_HIP(hipEventRecord(h->scratch_ev, s));
+    h->scratch_stream = s;
+    h->scratch_pending = true;
+    return SM_OK;
 }
 
 // Staged box path through AD (u8) + SAD (u16) volume workspaces, in launch groups of up to
@@ -1368,6 +1452,13 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         h->box_kernel = (int)value;
         return SM_OK;
     }
+    if (param == SM_PARAM_UNIQUENESS) {
+        const int v = (int)value;
+        if (!(value >= 0.f) || value > 99.f || (float)v != value)
+            return fail(SM_ERR_INVALID_ARG, "uniqueness ratio must be an integer in [0, 99] (0 = off)");
+        h->uniqueness = v;
+        return SM_OK;
+    }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);
 }
 
@@ -1472,6 +1563,145 @@ SM_API int sm_match_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d
     hipStream_t s = (hipStream_t)stream;
     return run_device(h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp, flags, d_disp,
                       out_pitch, out_frame_stride, nullptr, nullptr, width, (int64_t)width * height, s);
+}
+
+SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
+                                  int pitch, int batch, int64_t frame_stride, int radius, int num_disp, unsigned flags,
+                                  uint16_t* d_disp16, int out_pitch, int64_t out_frame_stride, uint16_t* d_right16,
+                                  uint8_t* d_mask, void* stream) {
+    int p1 = 0, p2 = 0;
+    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2);
+    if (rc) return rc;
+    if (!d_left || !d_right || !d_disp16) return fail(SM_ERR_INVALID_ARG, "null device pointer");
+    if (batch < 1) return fail(SM_ERR_INVALID_ARG, "batch %d < 1", batch);
+    if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
+    if (batch > 1 && (frame_stride < (int64_t)pitch * height || out_frame_stride < (int64_t)out_pitch * height))
+        return fail(SM_ERR_INVALID_ARG, "frame strides overlap");
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    rc = scratch_wait(h, s);
+    if (rc) return rc;
+    rc = run_subpix(h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp, flags, p1, p2,
+                    d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, s);
+    const int rc2 = scratch_record(h, s);
+    return rc ? rc : rc2;
+}
+
+SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
+                                     int pitch, int radius, int num_disp, unsigned flags, uint16_t* disp16_out,
+                                     uint16_t* right16_out, uint8_t* mask_out, int out_pitch) {
+    int p1 = 0, p2 = 0;
+    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2);
+    if (rc) return rc;
+    if (!left || !right || !disp16_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
+    if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
+    if (width > h->max_w || height > h->max_h || num_disp > h->max_d)
+        return fail(SM_ERR_CAPACITY, "frame %dx%d/D=%d exceeds handle capacity %dx%d/D=%d", width, height, num_disp,
+                    h->max_w, h->max_h, h->max_d);
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t P = (size_t)width * height;
+    if (h->aux_bytes < 5 * P) {   // [q u16][right q u16][mask u8]
+        if (h->d_aux) (void)hipFree(h->d_aux);
+        h->d_aux = nullptr;
+        h->aux_bytes = 0;
+        SM_HIP(hipMalloc(&h->d_aux, 5 * P));
+        h->aux_bytes = 5 * P;
+    }
+    uint16_t* dq = reinterpret_cast<uint16_t*>(h->d_aux);
+    uint16_t* dr = dq + P;
+    uint8_t* dm = h->d_aux + 4 * P;
+    rc = scratch_wait(h, s);
+    if (rc) return rc;
+    SM_HIP(copy2d(h->d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, s));
+    SM_HIP(copy2d(h->d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, s));
+    rc = run_subpix(h, h->d_left, h->d_right, width, height, width, 1, (int64_t)P, radius, num_disp, flags, p1, p2, dq,
+                    width, (int64_t)P, right16_out ? dr : nullptr, mask_out ? dm : nullptr, s);
+    const int rc2 = scratch_record(h, s);
+    if (rc || rc2) return rc ? rc : rc2;
+    const size_t row2 = (size_t)width * 2, op2 = (size_t)out_pitch * 2;
+    SM_HIP(copy2d(disp16_out, op2, dq, row2, row2, height, hipMemcpyDeviceToHost, s));
+    if (right16_out) SM_HIP(copy2d(right16_out, op2, dr, row2, row2, height, hipMemcpyDeviceToHost, s));
+    if (mask_out) SM_HIP(copy2d(mask_out, out_pitch, dm, width, width, height, hipMemcpyDeviceToHost, s));
+    SM_HIP(hipStreamSynchronize(s));
+    return SM_OK;
+}
+
+SM_API int sm_volume_wta_subpix_device(sm_handle* h, const void* d_vol, int elem_bytes, int width, int height,
+                                       int num_disp, uint32_t invalid_from, unsigned flags, uint16_t* d_disp16,
+                                       int out_pitch, uint16_t* d_right16, uint8_t* d_mask, void* stream) {
+    if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
+    if (width <= 0 || height <= 0) return fail(SM_ERR_INVALID_ARG, "bad frame size %dx%d", width, height);
+    if (num_disp < 1 || num_disp > sm::kMaxDisp)
+        return fail(SM_ERR_INVALID_ARG, "num_disp %d out of [1,%d]", num_disp, sm::kMaxDisp);
+    if (elem_bytes != 2 && elem_bytes != 4)
+        return fail(SM_ERR_INVALID_ARG, "elem_bytes %d: the volume holds uint16 (2) or uint32 (4) costs", elem_bytes);
+    if (flags & ~(unsigned)SM_LR_CHECK)
+        return fail(SM_ERR_INVALID_ARG, "sub-pixel WTA of a volume: flags are 0 or SM_LR_CHECK (0x%x)", flags);
+    if (!d_vol || !d_disp16) return fail(SM_ERR_INVALID_ARG, "null device pointer");
+    if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const bool lr = (flags & SM_LR_CHECK) != 0;
+    int rc = SM_OK;
+    if (lr) {   // the two views' d0 go through the LR workspace
+        rc = scratch_wait(h, s);
+        if (rc) return rc;
+        rc = ensure_lr(h, 2 * (size_t)width * height);
+        if (rc) return rc;
+    }
+    if (elem_bytes == 4)
+        SM_HIP(sm::launch_subpix_wta_u32(static_cast<const uint32_t*>(d_vol), width, height, num_disp, invalid_from,
+                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, h->d_lr, s));
+    else
+        SM_HIP(sm::launch_subpix_wta_u16(static_cast<const uint16_t*>(d_vol), width, height, num_disp, invalid_from,
+                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, h->d_lr, s));
+    return lr ? scratch_record(h, s) : SM_OK;
+}
+
+namespace {
+int reproject_check(const sm_handle* h, const void* disp16, int width, int height, int pitch, const double* Q,
+                    const void* xyz, int xyz_pitch) {
+    if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
+    if (width <= 0 || height <= 0) return fail(SM_ERR_INVALID_ARG, "bad frame size %dx%d", width, height);
+    if (!disp16 || !Q || !xyz) return fail(SM_ERR_INVALID_ARG, "null pointer");
+    if (pitch < width) return fail(SM_ERR_INVALID_ARG, "pitch %d < width %d", pitch, width);
+    if ((int64_t)xyz_pitch < 3 * (int64_t)width)
+        return fail(SM_ERR_INVALID_ARG, "xyz_pitch %d < 3 * width (%d floats per row)", xyz_pitch, 3 * width);
+    return SM_OK;
+}
+}  // namespace
+
+SM_API int sm_reproject_device(sm_handle* h, const uint16_t* d_disp16, int width, int height, int pitch,
+                               const double* Q, float* d_xyz, int xyz_pitch, void* stream) {
+    const int rc = reproject_check(h, d_disp16, width, height, pitch, Q, d_xyz, xyz_pitch);
+    if (rc) return rc;
+    SM_HIP(hipSetDevice(h->device));
+    SM_HIP(sm::launch_reproject(d_disp16, width, height, pitch, Q, d_xyz, xyz_pitch, (hipStream_t)stream));
+    return SM_OK;
+}
+
+SM_API int sm_reproject_u16(sm_handle* h, const uint16_t* disp16, int width, int height, int pitch, const double* Q,
+                            float* xyz_out, int xyz_pitch) {
+    int rc = reproject_check(h, disp16, width, height, pitch, Q, xyz_out, xyz_pitch);
+    if (rc) return rc;
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t P = (size_t)width * height;
+    rc = scratch_wait(h, s);
+    if (rc) return rc;
+    rc = ensure_vol(h, 16 * P);   // [xyz 12 P][q 2 P]
+    if (rc) return rc;
+    float* dx = reinterpret_cast<float*>(h->d_vol);
+    uint16_t* dq = reinterpret_cast<uint16_t*>(h->d_vol + 12 * P);
+    const size_t row2 = (size_t)width * 2, row12 = (size_t)width * 12;
+    SM_HIP(copy2d(dq, row2, disp16, (size_t)pitch * 2, row2, height, hipMemcpyHostToDevice, s));
+    SM_HIP(sm::launch_reproject(dq, width, height, width, Q, dx, 3 * width, s));
+    rc = scratch_record(h, s);
+    if (rc) return rc;
+    SM_HIP(copy2d(xyz_out, (size_t)xyz_pitch * 4, dx, row12, row12, height, hipMemcpyDeviceToHost, s));
+    SM_HIP(hipStreamSynchronize(s));
+    return SM_OK;
 }
 
 SM_API int sm_slice_keys_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,

@@ -130,12 +130,14 @@ enum {
     SM_PARAM_SGM_P2 = 5,       /* SM_AGG_SGM penalty of a larger step: an integer >= 0, 0 (default) = auto,
                                   32 * win^2.  P1 <= P2 and 255 * win^2 + P2 <= 65535 are checked by the matching
                                   call, against its radius (sm_sgm_check) */
-    SM_PARAM_BOX_KERNEL = 6    /* which kernel the plain box pass (no LR, no median workspace needed) runs: 0
+    SM_PARAM_BOX_KERNEL = 6,   /* which kernel the plain box pass (no LR, no median workspace needed) runs: 0
                                   (default) auto by launch size, 1 the VALU kernels at every size, 2 the
                                   matrix-pipe kernel at every size.  The maps and keys are the same bit for bit.
                                   The matrix-pipe kernel covers radius 1..7 without the fused right view: with
                                   SM_LR_CHECK, radius 0 or radius >= 8 the value 2 silently runs the VALU
                                   kernels.  Other values: SM_ERR_INVALID_ARG */
+    SM_PARAM_UNIQUENESS = 7    /* uniqueness ratio of the sub-pixel calls (sm_match_subpix_device and friends): an
+                                  integer 0..99, 0 (default) = off.  Other values: SM_ERR_INVALID_ARG */
 };
 
 typedef struct sm_handle sm_handle;
@@ -307,6 +309,57 @@ SM_API int sm_census_volume_device(sm_handle *h, const uint8_t *d_left, const ui
                                    int pitch, int num_disp, uint8_t *d_ham, void *stream);
 SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t *right, int width, int height,
                                int pitch, int num_disp, uint8_t *ham_out);
+
+/* ---- sub-pixel disparity: 1/16 px in uint16, uniqueness filter, 3-D reprojection (this build's extension) ----
+ * The rule, all integer.  A pixel's costs V(d) over the d that exist, d = 0 .. dmax:
+ *   left view   dmax = min(num_disp - 1, W - x);
+ *   right view  V_R(u, d) = V(u + d, d) over u + 2 d <= W (the pairs of the 8-bit SGM / census right view); the AD
+ *               box path (SM_AGG_BOX without SM_COST_CENSUS) takes u + d < W, its 8-bit right view's pairs.
+ *   d0    = the first (smallest) d at min V: the d of the 8-bit call with the same flags.
+ *   delta = floor((16 (a - c) + den) / (2 den)) with a = V(d0 - 1), b = V(d0), c = V(d0 + 1), den = a + c - 2 b
+ *           (>= 1: d0 is the first minimum) where 1 <= d0 < dmax, else 0: round-half-up of 8 (a - c) / den, a floor
+ *           division, in [-8, 8]; a two-wide plateau (c == b) gives +8.
+ *   q     = 16 d0 + delta <= 4088.
+ *   uniqueness u (SM_PARAM_UNIQUENESS, 1..99): the pixel is invalid if some existing d with |d - d0| > 1 has
+ *           V(d) * (100 - u) < b * 100 (StereoSGBM's strict comparison); each view with its own V.
+ *   threshold: with the AD cost under SM_AGG_BOX the left view is invalid where b >= 50 * win^2, as in the 8-bit
+ *           call (whose right view has no threshold either); none for SM_AGG_SGM or SM_COST_CENSUS.
+ *   SM_LR_CHECK: the 8-bit rule on the views' d0 (occluded when x - d < 0, d == 0 or |d - d0_R(x - d)| > 1), an
+ *           invalid pixel of either view counting as d0 = 0.  With uniqueness off the mask equals the 8-bit call's.
+ *   An invalid or occluded pixel gives q = 0 and mask = 0.  Without SM_LR_CHECK the mask is the left view's validity
+ *   and the right map is not needed unless asked for.  The right map is never checked (as in the 8-bit calls).
+ * The arithmetic is exact for V < 2^24 (the bound under which the 8-bit (V << 8 | d) key fits 32 bits).
+ *
+ * sm_match_subpix_device: flags SM_AGG_BOX or SM_AGG_SGM, optionally | SM_COST_CENSUS | SM_LR_CHECK; radius <= 7,
+ * width <= 4096.  SM_MEDIAN (the ctmf median is an 8-bit histogram), SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID
+ * (no cost volume to interpolate) return SM_ERR_INVALID_ARG before any device work.  d_disp16: [batch][height]
+ * [out_pitch], out_pitch and out_frame_stride in uint16 elements; d_right16 / d_mask: dense [batch][height][width],
+ * either may be NULL.  Frames of a batch run one after another through the handle's volume workspace:
+ * sm_sgm_workspace_bytes / sm_census_workspace_bytes as for the 8-bit call, 3 * P * num_disp + 4 * P (each part
+ * rounded up to 256) for the AD box path.  Asynchronous on `stream`.
+ * sm_block_match_subpix_u16: the same on one host frame, synchronous; out_pitch in elements for all three outputs.
+ * sm_volume_wta_subpix_device: the rule on a caller's d-major volume [num_disp][height][width] of uint16
+ * (elem_bytes 2) or uint32 (elem_bytes 4) costs < 2^24, right view over u + 2 d <= W, with the handle's uniqueness;
+ * invalid_from: 0 = no threshold, else the left view is invalid where b >= it; flags: 0 or SM_LR_CHECK (2 * P bytes
+ * of the handle's LR workspace). */
+SM_API int sm_match_subpix_device(sm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int width, int height,
+                                  int pitch, int batch, int64_t frame_stride, int radius, int num_disp,
+                                  unsigned flags, uint16_t *d_disp16, int out_pitch, int64_t out_frame_stride,
+                                  uint16_t *d_right16, uint8_t *d_mask, void *stream);
+SM_API int sm_block_match_subpix_u16(sm_handle *h, const uint8_t *left, const uint8_t *right, int width, int height,
+                                     int pitch, int radius, int num_disp, unsigned flags, uint16_t *disp16_out,
+                                     uint16_t *right16_out, uint8_t *mask_out, int out_pitch);
+SM_API int sm_volume_wta_subpix_device(sm_handle *h, const void *d_vol, int elem_bytes, int width, int height,
+                                       int num_disp, uint32_t invalid_from, unsigned flags, uint16_t *d_disp16,
+                                       int out_pitch, uint16_t *d_right16, uint8_t *d_mask, void *stream);
+/* reprojectImageTo3D for 1/16-px maps: for q > 0, d = q / 16 and (X, Y, Z, w) = Q (x, y, d, 1), evaluated in double;
+ * xyz[y][3 x ..] = (X / w, Y / w, Z / w) as fp32; q == 0 or w == 0 gives (0, 0, 0).  Q: row-major 4 x 4, as
+ * sm_stereo_rectify writes it.  pitch in uint16 elements, xyz_pitch in floats per row (>= 3 * width).
+ * sm_reproject_u16: host pointers, synchronous, any frame size. */
+SM_API int sm_reproject_device(sm_handle *h, const uint16_t *d_disp16, int width, int height, int pitch,
+                               const double *Q, float *d_xyz, int xyz_pitch, void *stream);
+SM_API int sm_reproject_u16(sm_handle *h, const uint16_t *disp16, int width, int height, int pitch, const double *Q,
+                            float *xyz_out, int xyz_pitch);
 
 /* u16 SAD volume sad[d][y][x] = zero-padded (2r+1)^2 window sum of the AD plane d, radius <= 7
  * (the volume kernalFindAllSAD / getAllSAD build, Device.cu:67-103 / BlockMatching.cpp:191-261,

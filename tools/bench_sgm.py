@@ -5,7 +5,11 @@ and that traffic over the time as a fraction of the 6.85 TB/s fill rate the proj
 (profiles/microbench/r05_write_ceiling.txt).  No GPU, no number: the script fails without one.
 
 --cost census times the census cost (SM_COST_CENSUS) under --agg sgm or box instead, beside AD SGM from the same run
-of the same build, and writes profiles/census_bench.json (ms per map only: DESIGN §18)."""
+of the same build, and writes profiles/census_bench.json (ms per map only: DESIGN §18).
+
+--subpix times the sub-pixel call (sm_match_subpix_device, uint16 maps in 1/16 px) alternated with the 8-bit call of
+the same flags, for AD SGM and census SGM without and with LR, with the uniqueness filter off and at 10, and writes
+profiles/subpix_bench.json (ms per map and the difference: DESIGN §20)."""
 import argparse
 import json
 import os
@@ -74,6 +78,50 @@ def census_main(a, sm, torch, Lt, Rt, out_t):
     return 0
 
 
+def subpix_main(a, sm, torch, Lt, Rt, out_t):
+    """ms per map of the sub-pixel call and of the 8-bit call of the same flags, alternated, two rounds."""
+    W, H, D, r = a.width, a.height, a.disp, a.radius
+    res = {"workload": {"width": W, "height": H, "num_disp": D, "radius": r, "agg": "sgm"},
+           "device": torch.cuda.get_device_name(0), "warmup": a.warmup, "iters": a.iters, "runs": {}}
+    out16 = torch.empty((H, W), dtype=torch.int16, device=Lt.device)
+
+    def time16(m, **kw):
+        for _ in range(a.warmup):
+            m.match_subpix_device(Lt, Rt, r, D, out_t=out16, **kw)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            m.match_subpix_device(Lt, Rt, r, D, out_t=out16, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+
+    with sm.BlockMatcher(0, W, H, D) as m:
+        for rnd in range(2):
+            for u in (0, 10):
+                m.set_uniqueness(u)
+                for cost in ("ad", "census"):
+                    for lr in (False, True):
+                        kw = dict(agg="sgm", cost=cost, lr_check=lr)
+                        ms8 = time_ms(torch, m, Lt, Rt, r, D, out_t, a.warmup, a.iters, **kw)
+                        ms16 = time16(m, **kw)
+                        run = res["runs"].setdefault(f"{cost}_sgm{'_lr' if lr else ''}_u{u}",
+                                                     {"ms_8bit": [], "ms_subpix": [], "ms_difference": []})
+                        run["ms_8bit"].append(round(ms8, 4))
+                        run["ms_subpix"].append(round(ms16, 4))
+                        run["ms_difference"].append(round(ms16 - ms8, 4))
+                        run["valid_pixels_subpix"] = int((out16 > 0).sum().item())
+                        run["valid_pixels_8bit"] = int((out_t > 0).sum().item())
+        m.set_uniqueness(0)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--width", type=int, default=1920)
@@ -84,14 +132,17 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--cost", default="ad", choices=["ad", "census"])
     ap.add_argument("--agg", default="sgm", choices=["sgm", "box"])
-    ap.add_argument("--out", default=None, help="default: profiles/sgm_bench.json, or census_bench.json with --cost census")
+    ap.add_argument("--subpix", action="store_true", help="time the sub-pixel call against the 8-bit call (AD and census SGM)")
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/sgm_bench.json, census_bench.json with --cost census, subpix_bench.json with --subpix")
     a = ap.parse_args(argv)
     if a.iters < 20:
         ap.error("--iters must be at least 20")
     if a.cost == "ad" and a.agg != "sgm":
         ap.error("--agg box is timed with --cost census only (the AD box path is bench.py's)")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "sgm_bench.json" if a.cost == "ad" else "census_bench.json")
+        name = "subpix_bench.json" if a.subpix else ("sgm_bench.json" if a.cost == "ad" else "census_bench.json")
+        a.out = os.path.join(ROOT, "profiles", name)
     import torch
     import gpu_stereo_matching_amd as sm
     if not torch.cuda.is_available():
@@ -101,6 +152,8 @@ def main(argv=None):
     L, R = sm.synth_pair(1234, W, H, D)
     Lt, Rt = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
     out_t = torch.empty_like(Lt)
+    if a.subpix:
+        return subpix_main(a, sm, torch, Lt, Rt, out_t)
     if a.cost == "census":
         return census_main(a, sm, torch, Lt, Rt, out_t)
     res = {"workload": {"width": W, "height": H, "num_disp": D, "radius": r, "penalties": sm.sgm_penalties(r)},
