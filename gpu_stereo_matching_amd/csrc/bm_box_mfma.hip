@@ -1,11 +1,14 @@
 // bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
-// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19).
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21).
 //
 // Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
 //
-// Tile: 64 x 64 input pixels from (x0 - R, y0 - R) -> TO x TO outputs, TO = 64 - 2R.  Four waves split the
-// tile's d range; each keeps its best keys for the whole tile in registers (64 VGPRs) in the accumulator
-// layout, folded once at the end through LDS.
+// Tile: 64 x 64 input pixels from (x0 - R, y0 - R) -> TOY x TOX outputs: 48 rows (three 16-row blocks; the
+// fourth would be an edge block and its best keys the registers the paired loop needs) and 64 - 2R columns in
+// NXB = 4 blocks (R = 7: 48 columns in 3).  Four waves split the tile's d range and walk it two disparities per pass:
+// one L read, two R reads, v_min3_u32 on the two keys of a pixel.  Each wave keeps its best keys for the whole
+// tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
+// most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -18,7 +21,8 @@
 //             C = 256 * (2R+1) * BIAS + d: the f32 accumulator is the key (S << 8 | d) < 2^24, and every partial
 //             sum stays an integer below 2^24 in magnitude, so the accumulation order does not matter.
 //   WTA       positive f32 bit patterns order like unsigned integers: min on the raw bits, ties to the smaller
-//             d as in Device.cu:57; one v_cvt_u32_f32 per output pixel in the epilogue, then the seed.
+//             d as in Device.cu:57 (the key's low byte is d, also within a pair); one v_cvt_u32_f32 per output
+//             pixel in the epilogue, then the seed.
 //
 // Operand layout (lane l, g = l >> 4): A holds row l & 15, k = 8g..8g+7; B holds column l & 15, k = 8g..8g+7;
 // C/D hold column l & 15, rows 4g..4g+3.  Stage 1's D (output row l & 15, image columns 4g..4g+3 of a
@@ -42,18 +46,29 @@ constexpr int kT = 64;          // input tile edge
 constexpr int kNW = 4;          // waves per workgroup, one per SIMD
 constexpr int kThreads = 64 * kNW;
 constexpr int kColB = 128;      // bytes per staged column (64 rows of f16)
-constexpr int kFoldStride = 65; // dwords per row of the fold plane
 constexpr uint32_t kInfBits = 0x7F800000u;
 
-template <int R, int DMAX>
+// NP: disparities per loop pass.  2: the paired loop on 48-row tiles.  1: one d per pass on 64 - 2R rows, for short
+// d ranges at small radii, where a tile's staging and fold outweigh its loop and fewer, larger tiles win
+template <int R, int DMAX, int NP>
 struct MG {
-    static constexpr int TO = kT - 2 * R;               // outputs per tile, each way
-    static constexpr int RC = kT + DMAX;                // staged right-band columns
+    static_assert(NP == 1 || NP == 2, "one or two disparities per pass");
+    // 16-row output blocks per tile: with two d per pass the fourth block's best keys are the registers the second
+    // disparity needs
+    static constexpr int NOB = NP == 2 ? 3 : 4;
+    // 16-column output blocks per tile: four, the last one cut at 64 - 2R columns, while it keeps at least 4 columns;
+    // at R = 7 (2 columns) three full blocks are faster (1080p D = 128, 32 frames: 1.376 against 1.421 ms)
+    static constexpr int NXB = (NP == 1 || R <= 6) ? 4 : 3;
+    static constexpr int TOY = NOB == 4 ? kT - 2 * R : 16 * NOB;   // output rows per tile
+    static constexpr int TOX = NXB == 4 ? kT - 2 * R : 16 * NXB;   // output columns per tile
+    static constexpr int FOLD = 16 * NXB + 1;                      // dwords per row of the fold plane
+    static constexpr int RC = kT + DMAX;                           // staged right-band columns
     static constexpr int RS_BYTES = RC * kColB;
     static constexpr int L_BYTES = kT * kColB;
     static constexpr int LDS_BYTES = RS_BYTES + L_BYTES;
     static constexpr int BIAS = ((2 * R + 1) * 255 + 1) / 2;
-    static_assert(kT * kFoldStride * 4 <= LDS_BYTES, "the fold plane aliases the staged tiles");
+    static_assert(TOY + 2 * R <= kT && TOX + 2 * R <= kT, "every output's window lies in the input tile");
+    static_assert(TOY * FOLD * 4 <= LDS_BYTES, "the fold plane aliases the staged tiles");
     static_assert(BIAS < 2048 && (2 * R + 1) * 255 - BIAS < 2048, "D1 exact in f16");
     static_assert((int64_t)(2 * R + 1) * (2 * R + 1) * 255 * 256 + 255 < (1 << 24), "keys exact in f32");
 };
@@ -119,9 +134,10 @@ __device__ __forceinline__ f4 mfma(u4 a, u4 b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
 }
 
-template <int R, int DMAX>
+template <int R, int DMAX, int NP>
 __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int tiles_x, int tiles_y) {
-    using G = MG<R, DMAX>;
+    using G = MG<R, DMAX, NP>;
+    constexpr int NXB = G::NXB, NOB = G::NOB;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t* rsm = smem;                  // [RC][64] f16, swizzled
     uint8_t* lsm = smem + G::RS_BYTES;    // [64][64] f16, swizzled
@@ -138,8 +154,8 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const int t = tile_id - frame * tiles;
     const int ty = t / tiles_x;
     const int tx = t - ty * tiles_x;
-    const int x0 = tx * G::TO;
-    const int y0 = ty * G::TO;
+    const int x0 = tx * G::TOX;
+    const int y0 = ty * G::TOY;
     const int W = a.W, H = a.H;
     const int d_lo = a.d_lo, d_hi = a.d_hi;
 
@@ -185,11 +201,11 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const float c2base = (float)(256 * (2 * R + 1) * G::BIAS);
 
     // best keys as f32 bit patterns: [output row block][output column block][column 4g + i], row l16
-    uint32_t best[4][4][4];
+    uint32_t best[NOB][NXB][4];
 #pragma unroll
-    for (int ob = 0; ob < 4; ++ob)
+    for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-        for (int xb = 0; xb < 4; ++xb)
+        for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
             for (int i = 0; i < 4; ++i) best[ob][xb][i] = kInfBits;
 
@@ -199,7 +215,7 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const int dw_lo = d_lo + (wave * nd) / kNW;
     const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
     // largest d valid for every output of the tile
-    const int d_free = W - (min(x0 + G::TO, W) - 1);
+    const int d_free = W - (min(x0 + G::TOX, W) - 1);
     // tiles with a column left of some d, a column past the image, or a partly valid d take the masked loop
     const bool masked_tile = (x0 - R < d_hi) || (x0 - R + kT > W) || (d_end - 1 > d_free);
 
@@ -209,67 +225,92 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
 
     auto run = [&](auto masked_c) {
         constexpr bool MASKED = decltype(masked_c)::value;
-        for (int d = dw_lo; d < dw_hi; ++d) {
-            const int k0 = l16 + DMAX + d_lo - d;
-            const int raddr = slot(k0, g);
-            // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the d-dependent
-            // zero (d >= 0) keeps the reads inside the loop
-            const int laddr_d = laddr + (int)((uint32_t)d >> 31);
-            const float c2v = c2base + (float)d;
-            const f4 c2 = {c2v, c2v, c2v, c2v};
-            const bool dm = MASKED && d > d_free;
-            // t[ob]: the packed D1 of two adjacent column blocks, a stage-2 B operand.  Even blocks go to its low
-            // half and odd blocks to its high half, so no half is ever copied; bh or bhs matches the order.  The
-            // last output block (cb == 4) pairs block 3 with the stale block 2: with the left block in the high
-            // half the stale columns meet only outputs past TO, which are never written
-            u4 t[4];
+        // NP = 2: two disparities per pass; an odd range ends with its last d twice (the same keys: min3 is
+        // unchanged, and no column outside the wave's own range is read)
+#pragma unroll 1
+        for (int d = dw_lo; d < dw_hi; d += NP) {
+            const int dd[2] = {d, min(d + 1, dw_hi - 1)};
+            int raddr[NP];
+            f4 c2[NP];
+            bool dm[NP];
 #pragma unroll
-            for (int cb = 0; cb <= 4; ++cb) {
+            for (int p = 0; p < NP; ++p) {
+                raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
+                const float c2v = c2base + (float)dd[p];
+                c2[p] = f4{c2v, c2v, c2v, c2v};
+                dm[p] = MASKED && dd[p] > d_free;
+            }
+            // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the d-dependent
+            // zero (d >= 0) keeps the reads inside the loop, once per pair
+            const int laddr_d = laddr + (int)((uint32_t)d >> 31);
+            // t[p][ob]: the packed D1 of two adjacent column blocks of disparity p, a stage-2 B operand.  Even blocks
+            // go to its low half and odd blocks to its high half, so no half is ever copied; bh or bhs matches the
+            // order.  With NXB = 4 the last output block (cb == 4) pairs block 3 with the stale block 2: with the
+            // left block in the high half the stale columns meet only outputs past TOX, which are never written
+            u4 t[NP][NOB];
+#pragma unroll
+            for (int cb = 0; cb <= NXB; ++cb) {
                 if (cb < 4) {
-                    const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr + cb * 16 * kColB);
-                    const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr ^ 64) + cb * 16 * kColB);
                     const u4 l0 = *reinterpret_cast<const u4*>(lsm + laddr_d + cb * 16 * kColB);
                     const u4 l1 = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ 64) + cb * 16 * kColB);
-                    u4 ad0 = abs_diff(l0, r0);
-                    u4 ad1 = abs_diff(l1, r1);
-                    if constexpr (MASKED) {
-                        const int c = x0 - R + 16 * cb + l16;
-                        const bool ok = c >= d && c < W;
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) {
-                            ad0[m] = ok ? ad0[m] : 0u;
-                            ad1[m] = ok ? ad1[m] : 0u;
+                    for (int p = 0; p < NP; ++p) {
+                        const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr[p] + cb * 16 * kColB);
+                        const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ 64) + cb * 16 * kColB);
+                        u4 ad0 = abs_diff(l0, r0);
+                        u4 ad1 = abs_diff(l1, r1);
+                        if constexpr (MASKED) {
+                            const int c = x0 - R + 16 * cb + l16;
+                            const bool ok = c >= dd[p] && c < W;
+#pragma unroll
+                            for (int m = 0; m < 4; ++m) {
+                                ad0[m] = ok ? ad0[m] : 0u;
+                                ad1[m] = ok ? ad1[m] : 0u;
+                            }
+                        }
+                        // output row blocks 0..NOB-1 of this column block from the two 32-row chunks
+                        f4 sv[4];
+                        sv[0] = mfma(ad0, bv0, c1);
+                        sv[1] = mfma(ad0, bvm, c1);
+                        sv[1] = mfma(ad1, bvp, sv[1]);
+                        sv[2] = mfma(ad1, bv0, c1);
+                        if constexpr (NOB == 4) sv[3] = mfma(ad1, bvm, c1);
+#pragma unroll
+                        for (int ob = 0; ob < NOB; ++ob) {
+                            const uint2 pk = pack_f16(sv[ob]);
+                            t[p][ob][2 * (cb & 1)] = pk.x;
+                            t[p][ob][2 * (cb & 1) + 1] = pk.y;
                         }
                     }
-                    // output row blocks 0..3 of this column block from the two 32-row chunks
-                    f4 s0 = mfma(ad0, bv0, c1);
-                    f4 s1 = mfma(ad0, bvm, c1);
-                    s1 = mfma(ad1, bvp, s1);
-                    f4 s2 = mfma(ad1, bv0, c1);
-                    f4 s3 = mfma(ad1, bvm, c1);
-                    const f4 sv[4] = {s0, s1, s2, s3};
-#pragma unroll
-                    for (int ob = 0; ob < 4; ++ob) {
-                        const uint2 p = pack_f16(sv[ob]);
-                        t[ob][2 * (cb & 1)] = p.x;
-                        t[ob][2 * (cb & 1) + 1] = p.y;
-                    }
                 }
+                // NP = 2: the scheduler takes stage 1 and stage 2 of a column block as regions of their own: over the
+                // whole pass its latency-hiding order needs more than 168 registers and it falls back to source order
+                // (65 s_nop per pass instead of 20)
+                if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
                 if (cb >= 1) {
                     const int xb = cb - 1;
 #pragma unroll
-                    for (int ob = 0; ob < 4; ++ob) {
-                        const u4 o = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[ob], c2));
+                    for (int ob = 0; ob < NOB; ++ob) {
+                        u4 o[NP];
+#pragma unroll
+                        for (int p = 0; p < NP; ++p)
+                            o[p] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2[p]));
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            uint32_t k = o[i];
-                            if constexpr (MASKED) {
-                                if (dm) k = (d <= W - (x0 + 16 * xb + 4 * g + i)) ? k : kInfBits;
+                            uint32_t k = kInfBits;
+#pragma unroll
+                            for (int p = 0; p < NP; ++p) {
+                                uint32_t kp = o[p][i];
+                                if constexpr (MASKED) {
+                                    if (dm[p]) kp = dd[p] <= W - (x0 + 16 * xb + 4 * g + i) ? kp : kInfBits;
+                                }
+                                k = p == 0 ? kp : min(k, kp);
                             }
-                            best[ob][xb][i] = min(best[ob][xb][i], k);
+                            best[ob][xb][i] = min(best[ob][xb][i], k);   // NP = 2: v_min3_u32
                         }
                     }
                 }
+                if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
@@ -279,37 +320,37 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
 
     // ---- fold the waves (same lane = same pixels in every wave) through one LDS plane ----
-    uint32_t* fold = reinterpret_cast<uint32_t*>(smem);   // [64][kFoldStride] f32 bit patterns
+    uint32_t* fold = reinterpret_cast<uint32_t*>(smem);   // [TOY][FOLD] f32 bit patterns
     if (wave == 0) {
 #pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
+        for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-            for (int xb = 0; xb < 4; ++xb)
+            for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    fold[(16 * ob + l16) * kFoldStride + 16 * xb + 4 * g + i] = best[ob][xb][i];
+                    fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i] = best[ob][xb][i];
     }
     __syncthreads();
     if (wave != 0) {
 #pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
+        for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-            for (int xb = 0; xb < 4; ++xb)
+            for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    atomicMin(&fold[(16 * ob + l16) * kFoldStride + 16 * xb + 4 * g + i], best[ob][xb][i]);
+                    atomicMin(&fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i], best[ob][xb][i]);
     }
     __syncthreads();
     uint8_t* Df = a.disp ? a.disp + (int64_t)frame * a.out_frame_stride : nullptr;
     uint32_t* Kf = a.keys ? a.keys + (int64_t)frame * W * H : nullptr;
     // lane = output column, rows over the waves
-    if (lane < G::TO && x0 + lane < W) {
-        const int ylim = min(G::TO, H - y0);
+    if (lane < G::TOX && x0 + lane < W) {
+        const int ylim = min(G::TOY, H - y0);
         uint8_t* drow = Df ? Df + (int64_t)y0 * a.out_pitch + x0 + lane : nullptr;
         uint32_t* krow = Kf ? Kf + (int64_t)y0 * W + x0 + lane : nullptr;
         for (int j = wave; j < ylim; j += kNW) {
             // the f32 key to its integer (+inf: no valid d), then the seed
-            const uint32_t kb = fold[j * kFoldStride + lane];
+            const uint32_t kb = fold[j * G::FOLD + lane];
             const uint32_t kf = kb >= kInfBits ? 0xFFFFFFFFu : (uint32_t)__builtin_bit_cast(float, kb);
             const uint32_t k = min(kf, a.seed_key);
             if (drow) drow[(int64_t)j * a.out_pitch] = k < a.thresh_key ? (uint8_t)(k & 0xFFu) : (uint8_t)0;
@@ -318,16 +359,27 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     }
 }
 
-template <int R, int DMAX>
-hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s) {
-    using G = MG<R, DMAX>;
-    const int tiles_x = (a.W + G::TO - 1) / G::TO;
-    const int tiles_y = (a.H + G::TO - 1) / G::TO;
+template <int R, int DMAX, int NP>
+hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s) {
+    using G = MG<R, DMAX, NP>;
+    const int tiles_x = (a.W + G::TOX - 1) / G::TOX;
+    const int tiles_y = (a.H + G::TOY - 1) / G::TOY;
     const int64_t blocks = (int64_t)tiles_x * tiles_y * batch;
     if (blocks <= 0 || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((box_mfma_kernel<R, DMAX>), dim3((unsigned)blocks), dim3(kThreads), (size_t)G::LDS_BYTES, s, a,
-                       tiles_x, tiles_y);
+    hipLaunchKernelGGL((box_mfma_kernel<R, DMAX, NP>), dim3((unsigned)blocks), dim3(kThreads), (size_t)G::LDS_BYTES, s,
+                       a, tiles_x, tiles_y);
     return hipGetLastError();
+}
+
+template <int R, int DMAX>
+hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s) {
+    // short ranges at r <= 2 keep one d per pass on 62- / 60-row tiles: 1080p x 32 frames, D = 8 r = 1 0.206 against
+    // 0.221 ms, D = 32 r = 2 0.396 against 0.404; from r = 3 or D = 48 on the paired loop is level or ahead
+    // (profiles/microbench/box_mfma_pairs_ab.txt)
+    if constexpr (DMAX == 64 && R <= 2) {
+        if (a.d_hi - a.d_lo <= 32) return launch_rdp<R, DMAX, 1>(a, batch, s);
+    }
+    return launch_rdp<R, DMAX, 2>(a, batch, s);
 }
 
 template <int R>
