@@ -80,7 +80,7 @@ hipError_t launch_lr_check(const uint8_t* left_disp, int lpitch, int64_t lstride
 hipError_t launch_ad_volume(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int64_t fstride, int batch,
                             int D, uint8_t* dif, int64_t dstride, hipStream_t s);
 // staged box path (bm_staged.hip): u16 SAD volume from the AD volume, and WTA over the SAD volume
-// `ad` must have 8 readable bytes past its last plane (ensure_vol pads the handle's volume)
+// `ad` must have 8 readable bytes past its last plane (the handle's volume buffer carries that slack, sm_handle.h)
 hipError_t launch_box_sad_volume(const uint8_t* ad, int W, int H, int radius, int D, uint16_t* sad, hipStream_t s);
 // getAllSAD's pixel-major uchar volume out[p * D + d] (255 where x + d > W): from the u16 SAD volume
 // (radius <= 7), or computed directly at any radius

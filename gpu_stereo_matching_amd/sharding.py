@@ -322,7 +322,7 @@ def band_rows(height: int, rank: int, world: int) -> Tuple[int, int]:
 MEDIAN_RADIUS = 3   # SM_MEDIAN: 7x7 post-filter (StereoDisparity.cpp:85)
 
 
-BAND_ALIGN = 32   # band inputs start on the frame's 32-row tile grid (sm_capi.hip group_bands)
+BAND_ALIGN = 32   # band inputs start on the frame's 32-row tile grid (sm_capi_group.hip group_bands)
 
 
 def band_halo(radius: int, agg: str = "box", median: bool = False) -> int:

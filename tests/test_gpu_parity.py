@@ -347,6 +347,50 @@ def test_two_streams_one_handle_wide(matcher, oracle, torch, r):
             assert np.array_equal(o.cpu().numpy(), w)
 
 
+def _two_streams_volume_against_match(sm, oracle, torch, volume_call, match_kw):
+    """One handle, two streams, 3 repetitions: `volume_call(m, L, R, stream)` on a 320x96 D=32 pair on stream 1 and
+    match_device(**match_kw) on a 400x120 D=48 pair on stream 2.  Each repetition takes a fresh handle, so the larger
+    second pass grows the volume workspace behind the first every time.  Both results must equal the same calls
+    made one at a time."""
+    r = 2
+    (W1, H1, D1), (W2, H2, D2) = (320, 96, 32), (400, 120, 48)
+    a = [torch.from_numpy(x).cuda() for x in oracle.synth_pair(81, W1, H1, D1)]
+    b = [torch.from_numpy(x).cuda() for x in oracle.synth_pair(82, W2, H2, D2)]
+    with sm.BlockMatcher(0, W2, H2, D2) as m:   # the reference: one call at a time
+        want_vol = volume_call(m, a[0], a[1], None)
+        torch.cuda.synchronize()
+        want_map = m.match_device(b[0], b[1], r, D2, **match_kw)
+        torch.cuda.synchronize()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for _ in range(3):
+        with sm.BlockMatcher(0, W2, H2, D2) as m:
+            vol = volume_call(m, a[0], a[1], s1)
+            out = m.match_device(b[0], b[1], r, D2, stream=s2, **match_kw)
+            torch.cuda.synchronize()
+            assert torch.equal(vol, want_vol)
+            assert torch.equal(out, want_map)
+
+
+def test_two_streams_sad_volume_against_sgm_lr(sm, oracle, torch):
+    """sm_sad_volume_device writes (and may grow) the handle's volume workspace on the caller's stream; it is now
+    ordered against the other workspace passes.  sad_volume_device (320x96, r = 2, D = 32) on one stream and an
+    SGM + LR match_device on a larger pair (400x120, D = 48, which grows the workspace behind the first) on another
+    must both give what they give one at a time.  This cannot prove the absence of a race; it runs the newly
+    ordered paths, the grow included."""
+    _two_streams_volume_against_match(
+        sm, oracle, torch, lambda m, L, R, s: m.sad_volume_device(L, R, 2, 32, stream=s),
+        dict(agg="sgm", lr_check=True))
+
+
+def test_two_streams_census_volume_against_census_lr(sm, oracle, torch):
+    """The same for sm_census_volume_device (its two census images live in the volume workspace) against a census
+    box + LR match_device on the larger pair.  As above, this cannot prove the absence of a race; it runs the newly
+    ordered paths, the grow included."""
+    _two_streams_volume_against_match(
+        sm, oracle, torch, lambda m, L, R, s: m.census_volume_device(L, R, 32, stream=s),
+        dict(cost="census", lr_check=True))
+
+
 def test_out_tensor_validation(matcher, torch):
     """a caller-supplied output of the wrong shape / dtype / device is a ValueError, never
     an out-of-bounds device write."""

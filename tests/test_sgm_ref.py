@@ -80,6 +80,27 @@ def test_workspace_bytes():
     assert _rc_ws(64, 64, 16, 2, 0, None) == 1   # null output pointer
 
 
+def _up(n):
+    return (n + 255) // 256 * 256
+
+
+@pytest.mark.parametrize("W,H,D,sgm,census_box,census_sgm", [
+    (37, 5, 3, 4352, 5888, 7424),                           # every part a non-multiple of 256
+    (320, 256, 64, 31784960, 17367040, 33095680),
+    (1920, 1080, 128, 1600819200, 837734400, 1633996800),
+])
+def test_workspace_layout_totals(W, H, D, sgm, census_box, census_sgm):
+    """The volume workspace's one layout (volume_layout, csrc/sm_handle.h) through the exported functions, no
+    device needed: the totals are the sums of their 256-B aligned parts, and equal the values the library gave
+    before the SGM and census layouts were merged (the literals)."""
+    import gpu_stereo_matching_amd as sm
+    P = W * H
+    assert sm.sgm_workspace_bytes(W, H, D, 2) == _up(4 * P * D) + _up(2 * P * D) + _up(4 * P) == sgm
+    assert sm.census_workspace_bytes(W, H, D, 2) == \
+        _up(P * D) + _up(2 * P * D) + _up(4 * P) + 2 * _up(8 * P) == census_box
+    assert sm.census_workspace_bytes(W, H, D, 2, agg="sgm") == sgm + 2 * _up(8 * P) == census_sgm
+
+
 def _rc_ws(W, H, D, r, p2, out):
     from gpu_stereo_matching_amd import _capi
     return _capi.load().sm_sgm_workspace_bytes(W, H, D, r, p2, out)
