@@ -1,5 +1,5 @@
 // bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
-// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21).
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22).
 //
 // Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
 //
@@ -13,7 +13,8 @@
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
 //             clearing the sign bits gives AD in 0..255.  Rows outside the image stage 0 on both sides (AD 0);
-//             columns with c < d or c >= W get AD = 0 by one select per AD register, in the tiles that have any.
+//             columns with c < d or c >= W get AD = 0 from the AND that clears the sign bits (a lane is one column),
+//             and outputs with d > W - x start stage 2 from +inf, in the passes that have any.
 //   stage 1   (vertical, M = 16 image columns, K = 32 input rows, N = 16 output rows)
 //             D1 = sum AD - BIAS, BIAS = ceil((2R+1) * 255 / 2) in the C operand: |D1| <= 1913 < 2048 at R = 7,
 //             so v_cvt_pk to f16 is exact.
@@ -112,13 +113,17 @@ __device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xle
     }
 }
 
-__device__ __forceinline__ u4 abs_diff(u4 l, u4 r) {
+constexpr uint32_t kAbsBits = 0x7FFF7FFFu;
+
+// |l - r| of eight staged pixels: v_pk_add_f16 with neg on r, then `keep` = kAbsBits clears the two sign bits; a
+// lane whose image column is invalid passes keep = 0 and gets AD = 0 from the same AND
+__device__ __forceinline__ u4 abs_diff(u4 l, u4 r, uint32_t keep) {
     u4 ad;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {   // v_pk_add_f16 with neg on r, then the two sign bits
+    for (int m = 0; m < 4; ++m) {
         const uint32_t lm = l[m], rm = r[m];
         const h2 d = __builtin_bit_cast(h2, lm) - __builtin_bit_cast(h2, rm);
-        ad[m] = __builtin_bit_cast(uint32_t, d) & 0x7FFF7FFFu;
+        ad[m] = __builtin_bit_cast(uint32_t, d) & keep;
     }
     return ad;
 }
@@ -216,29 +221,35 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
     // largest d valid for every output of the tile
     const int d_free = W - (min(x0 + G::TOX, W) - 1);
-    // tiles with a column left of some d, a column past the image, or a partly valid d take the masked loop
-    const bool masked_tile = (x0 - R < d_hi) || (x0 - R + kT > W) || (d_end - 1 > d_free);
+    // Both masks are monotone in d: a staged column c needs AD = 0 where c < d (from d = x0 - R + 1 on) or c >= W
+    // (every d), an output column x has no key where d > W - x (from d = d_free + 1 on).  d_m is the first
+    // disparity of the tile that needs either; each wave walks the whole passes below it in the unmasked loop and
+    // the rest of its range in a masked one
+    const int d_m = (x0 - R + kT > W) ? d_lo : max(min(x0 - R, d_free) + 1, d_lo);
+    const int n_free = max(min(dw_hi, d_m) - dw_lo, 0);
+    const int dw_m = dw_lo + n_free - n_free % NP;
 
     const int laddr = slot(l16, g);   // + 16 columns per block; chunk 1 is ^ 64
 
     __syncthreads();
 
-    auto run = [&](auto masked_c) {
+    // one loop over [lo, hi); MASKED: with the c >= d and c < W mask of the staged columns and the d <= W - x mask of
+    // the outputs
+    auto run = [&](auto masked_c, const int lo, const int hi) {
         constexpr bool MASKED = decltype(masked_c)::value;
         // NP = 2: two disparities per pass; an odd range ends with its last d twice (the same keys: min3 is
-        // unchanged, and no column outside the wave's own range is read)
+        // unchanged, and no column outside the loop's own range is read)
 #pragma unroll 1
-        for (int d = dw_lo; d < dw_hi; d += NP) {
-            const int dd[2] = {d, min(d + 1, dw_hi - 1)};
+        for (int d = lo; d < hi; d += NP) {
+            const int dd[2] = {d, min(d + 1, hi - 1)};
             int raddr[NP];
+            float c2v[NP];
             f4 c2[NP];
-            bool dm[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
-                const float c2v = c2base + (float)dd[p];
-                c2[p] = f4{c2v, c2v, c2v, c2v};
-                dm[p] = MASKED && dd[p] > d_free;
+                c2v[p] = c2base + (float)dd[p];
+                c2[p] = f4{c2v[p], c2v[p], c2v[p], c2v[p]};
             }
             // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the d-dependent
             // zero (d >= 0) keeps the reads inside the loop, once per pair
@@ -257,17 +268,16 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
                     for (int p = 0; p < NP; ++p) {
                         const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr[p] + cb * 16 * kColB);
                         const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ 64) + cb * 16 * kColB);
-                        u4 ad0 = abs_diff(l0, r0);
-                        u4 ad1 = abs_diff(l1, r1);
+                        // a lane is one image column for all eight AD registers: its mask rides on their AND
+                        uint32_t keep = kAbsBits;
+                        // (d <= c < W as one unsigned compare: d <= W in every pass.  The scalar part goes through
+                        // readfirstlane so that no per-lane part of it is hoisted and held over the loop)
                         if constexpr (MASKED) {
-                            const int c = x0 - R + 16 * cb + l16;
-                            const bool ok = c >= dd[p] && c < W;
-#pragma unroll
-                            for (int m = 0; m < 4; ++m) {
-                                ad0[m] = ok ? ad0[m] : 0u;
-                                ad1[m] = ok ? ad1[m] : 0u;
-                            }
+                            const int c0 = __builtin_amdgcn_readfirstlane(x0 - R + 16 * cb - dd[p]);
+                            keep = (uint32_t)(l16 + c0) < (uint32_t)(W - dd[p]) ? kAbsBits : 0u;
                         }
+                        const u4 ad0 = abs_diff(l0, r0, keep);
+                        const u4 ad1 = abs_diff(l1, r1, keep);
                         // output row blocks 0..NOB-1 of this column block from the two 32-row chunks
                         f4 sv[4];
                         sv[0] = mfma(ad0, bv0, c1);
@@ -289,23 +299,33 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
                 if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
                 if (cb >= 1) {
                     const int xb = cb - 1;
+                    // an output column past W - d starts from +inf: the products are finite, so its accumulator
+                    // stays +inf (kInfBits exactly) for every row block, and the min and the epilogue read it as
+                    // "no valid d".  Built per column block, so it is not held over the pass
+                    f4 c2x[NP];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        c2x[p] = c2[p];
+                        if constexpr (MASKED) {
+                            // element i is output column x0 + 16 xb + 4g + i, valid for d <= W - x.  No scalar skip
+                            // of blocks that are valid throughout: a branch inside the pass spills
+                            const int e = __builtin_amdgcn_readfirstlane(W - x0 - 16 * xb - dd[p]) - 4 * g;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                c2x[p][i] = i <= e ? c2v[p] : __builtin_bit_cast(float, kInfBits);
+                        }
+                    }
 #pragma unroll
                     for (int ob = 0; ob < NOB; ++ob) {
                         u4 o[NP];
 #pragma unroll
                         for (int p = 0; p < NP; ++p)
-                            o[p] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2[p]));
+                            o[p] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2x[p]));
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            uint32_t k = kInfBits;
+                            uint32_t k = o[0][i];
 #pragma unroll
-                            for (int p = 0; p < NP; ++p) {
-                                uint32_t kp = o[p][i];
-                                if constexpr (MASKED) {
-                                    if (dm[p]) kp = dd[p] <= W - (x0 + 16 * xb + 4 * g + i) ? kp : kInfBits;
-                                }
-                                k = p == 0 ? kp : min(k, kp);
-                            }
+                            for (int p = 1; p < NP; ++p) k = min(k, o[p][i]);
                             best[ob][xb][i] = min(best[ob][xb][i], k);   // NP = 2: v_min3_u32
                         }
                     }
@@ -314,8 +334,8 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
             }
         }
     };
-    if (masked_tile) run(std::true_type{});
-    else run(std::false_type{});
+    run(std::false_type{}, dw_lo, dw_m);
+    run(std::true_type{}, dw_m, dw_hi);
 
     __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
 
