@@ -455,8 +455,8 @@ SM_API int sm_last_segment_tree_stats(sm_handle* h, float* tree_ms, float* total
 SM_API int sm_last_segment_tree_arrays(sm_handle* h, int* ints, int64_t n_ints, uint8_t* pdist, int64_t n_bytes,
                                        int* levels) {
     if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
-    if (!h->st_valid || h->st.last_P <= 0) return fail(SM_ERR_INVALID_ARG, "no segment-tree call has completed on this handle");
-    const int64_t P = h->st.last_P, nlev = h->st.last_nlev, need = 4 * P + nlev + 1;
+    if (!h->st_valid || h->st.last_pixels() <= 0) return fail(SM_ERR_INVALID_ARG, "no segment-tree call has completed on this handle");
+    const int64_t P = h->st.last_pixels(), need = h->st.last_tree_ints();
     // n_bytes must be the last call's pixel count exactly: a caller slicing the ints by its own width *
     // height would mis-slice them after a call on another frame shape
     if (!ints || !pdist || n_ints < need || n_bytes != P)
@@ -464,9 +464,8 @@ SM_API int sm_last_segment_tree_arrays(sm_handle* h, int* ints, int64_t n_ints, 
                     (long long)need, (long long)P);
     SM_HIP(hipSetDevice(h->device));
     SM_HIP(hipStreamSynchronize(h->stream));
-    SM_HIP(hipMemcpy(ints, h->st.tree_i, (size_t)need * sizeof(int), hipMemcpyDeviceToHost));
-    SM_HIP(hipMemcpy(pdist, h->st.tree_b, (size_t)P, hipMemcpyDeviceToHost));
-    if (levels) *levels = (int)nlev;
+    SM_HIP(h->st.copy_last_tree(ints, pdist));
+    if (levels) *levels = h->st.last_levels();
     return SM_OK;
 }
 

@@ -35,7 +35,7 @@ extern "C" int st_host_tree_depth(const uint8_t* wr, const uint8_t* wu, const ui
     return export_tree(t, P, node, parent, pdist);
 }
 
-// The device path's neighbour lists (bm_segtree.hip st_adj_kernel: per pixel, its marked grid edges at
+// The device path's neighbour lists (bm_segtree_build.hip st_adj_kernel: per pixel, its marked grid edges at
 // their sorted positions, in position order, distances from the marks' penalty bit) restated here on
 // the marks of segment_passes, against segment_lists' lists built during the second pass.  depth != 0:
 // the colour + depth weights of st_host_tree_depth (disp, mask, level), scale 255.  Returns the number of

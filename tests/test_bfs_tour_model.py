@@ -1,4 +1,4 @@
-"""The device BFS's algorithm (csrc/bm_segtree.hip, gpu_bfs) restated in plain Python and checked
+"""The device BFS's algorithm (csrc/bm_segtree_build.hip, gpu_bfs) restated in plain Python and checked
 against a FIFO BFS (SegmentTree.cpp:97-130's order: from pixel 0, a node's children in neighbour-list
 order) on random spanning trees of small grids.  It pins the math the kernels implement: the Euler tour
 built from the lists, ranking it roots the tree (parent = the neighbour whose arc comes first, subtree

@@ -109,6 +109,39 @@ def test_stmatch_cli(oracle, tmp_path, method):
     assert np.array_equal(got, want)
 
 
+def test_workspace_grows_and_is_reused_across_methods(oracle):
+    """One fresh handle through ST-2 and ST-1 calls ordered so that every workspace buffer of both slots
+    grows after the other method used it at a smaller size, and is then reused while oversized (the
+    smallest frames of this suite: 2 pixels wide, one row, W < D); every map bit-exact.  The tree arrays
+    follow the last call's shape.  Then a second handle after the first is closed."""
+    import gpu_stereo_matching_amd as sm
+
+    def pair(W, H, seed):
+        rng = np.random.default_rng(seed)
+        L = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        L[: H // 2, : W // 3] = 77
+        R = np.roll(L, -min(5, W - 1), axis=1)
+        R[:, -3:] = rng.integers(0, 256, (H, min(3, W), 3), dtype=np.uint8)
+        return L, R
+
+    def check(m, method, W, H, D, seed):
+        L, R = pair(W, H, seed)
+        want = (oracle.st2_disp if method else oracle.st_disp)(L, R, D, 2, 0.1)[0]
+        got = m.segment_tree(L, R, D, 2, 0.1, method=method)
+        assert np.array_equal(got, want), (method, W, H, D, int((got != want).sum()))
+
+    steps = [(1, 64, 48, 16), (0, 300, 200, 64), (1, 2, 5, 3), (0, 123, 1, 9), (1, 300, 200, 64), (0, 64, 48, 16)]
+    with sm.BlockMatcher(0, 320, 208, 64) as m:
+        for i, (method, W, H, D) in enumerate(steps):
+            check(m, method, W, H, D, 40 + i)
+            if i == 4:
+                assert len(m.segment_tree_arrays(300, 200)["rank"]) == 300 * 200
+                with pytest.raises(sm.SMError):
+                    m.segment_tree_arrays(64, 48)
+    with sm.BlockMatcher(0, 320, 208, 64) as m:
+        check(m, *steps[0], 40)
+
+
 def test_workgroup_filter_fallback():
     """The workgroup-per-disparity filter (st_filter_kernel), which trees wider than the wave filter's
     LDS buffers take, forced by SM_ST_WAVE_FILTER=0 in a child process: ST-1 and ST-2 bit-exact."""
@@ -147,7 +180,7 @@ def _bfs_cases():
 
 @pytest.mark.parametrize("method", [0, 1])
 def test_device_bfs_equals_host_bfs(matcher, method):
-    """The BFS on the GPU (Euler tour + pointer jumping + depth sort, bm_segtree.hip) against the host's
+    """The BFS on the GPU (Euler tour + pointer jumping + depth sort, bm_segtree_build.hip) against the host's
     BFS (st_host::bfs_tree, SM_ST_HOST_BFS=1, itself checked against oracle/st_oracle.c by
     tests/test_st_host.py): the tree arrays the filter reads (rank, parent, first, child words, level
     offsets, parent distances) identical, for ST-1's colour tree and ST-2's colour + depth tree, and the
