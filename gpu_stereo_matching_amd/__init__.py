@@ -192,6 +192,12 @@ class BlockMatcher:
         radius 0, radius >= 8) runs the VALU kernels."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_KERNEL, float(kernel)))
 
+    def set_box_workgroups(self, n=0):
+        """Workgroups of a matrix-pipe box launch (SM_PARAM_BOX_WORKGROUPS): 0 auto, n >= 1 that many, each walking
+        a contiguous range of tiles and keeping the right band along a row; at most one per tile, so n >= tiles is one
+        tile per workgroup.  Same maps and keys at every n; the VALU kernels ignore it."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_WORKGROUPS, float(n)))
+
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
                         lr_check: bool = False) -> np.ndarray:
         """The d-slice split of BlockMatcherGroup.match_dslice with `members` members, run one after

@@ -34,6 +34,7 @@ SM_PARAM_SGM_P1 = 4
 SM_PARAM_SGM_P2 = 5
 SM_PARAM_BOX_KERNEL = 6
 SM_PARAM_UNIQUENESS = 7
+SM_PARAM_BOX_WORKGROUPS = 8
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (

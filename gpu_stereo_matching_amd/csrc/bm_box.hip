@@ -659,7 +659,8 @@ bool box_mfma_enabled() {
 // box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the kernels of this file, 2 the matrix-pipe kernel
 // (bm_box_mfma.hip) at any launch size; outside that kernel's scope (the right view, r = 0, r > 7) 2 is 0
 template <int R, int DMAX, bool RIGHT>
-hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel) {
+hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel,
+                     int box_workgroups = 0) {
     using G = Geo<R, DMAX, kWavesD<RIGHT, R, DMAX>>;
     const int tiles_x = (a.W + G::TW - 1) / G::TW;
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
@@ -683,7 +684,7 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         // overlaps no other tile's compute (1080p batch 1: 102.8 vs 87.8 us).
         const int npairs = ((a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1)) / 2;
         const bool mfma_ok = R >= 1 && R <= kMaxFastRadius && box_mfma_scope(a);
-        if (mfma_ok && box_kernel == 2) return launch_box_match_mfma(a, batch, s);
+        if (mfma_ok && box_kernel == 2) return launch_box_match_mfma(a, batch, s, box_workgroups);
         if constexpr (!kWideR<R>) {
             if (wide_tiles_enabled() && blocks <= compute_units() && npairs >= 2 * kWideTile) {
                 using GW = Geo<R, DMAX, kWideTile>;
@@ -706,7 +707,7 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         // (profiles/microbench/box_mfma_headline_ab.txt)
         if (mfma_ok && box_kernel == 0 && box_mfma_enabled() &&
             blocks > (int64_t)(mid_tiles_max() > 0 ? mid_tiles_max() : 8) * compute_units())
-            return launch_box_match_mfma(a, batch, s);
+            return launch_box_match_mfma(a, batch, s, box_workgroups);
         hipLaunchKernelGGL((box_match_kernel<R, DMAX, false>), dim3((unsigned)blocks), dim3(64 * kWaves<false, R>),
                            (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
     }
@@ -714,14 +715,15 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
 }
 
 template <int R, bool RIGHT>
-hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel = 0) {
+hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel = 0,
+                    int box_workgroups = 0) {
     const int dspan = (a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1);
-    if (dspan <= 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel);
-    if (dspan <= 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel);
+    if (dspan <= 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    if (dspan <= 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
     // 192 (cfg5): the right band and the right-key rows sized for 192, not 256, keep the plain kernel
     // at 4 workgroups/CU and the right-view kernel at 2
-    if (dspan <= 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel);
-    return launch_rd<R, 256, RIGHT>(a, batch, ro, s, box_kernel);
+    if (dspan <= 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    return launch_rd<R, 256, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
 }
 
 template <int R>
@@ -776,24 +778,24 @@ __global__ __launch_bounds__(256) void box_match_generic_kernel(MatchArgs a, int
 
 }  // namespace
 
-hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel) {
+hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel, int box_workgroups) {
     switch (a.radius) {
-        case 0: return launch_r<0, false>(a, batch, nullptr, s, box_kernel);
-        case 1: return launch_r<1, false>(a, batch, nullptr, s, box_kernel);
-        case 2: return launch_r<2, false>(a, batch, nullptr, s, box_kernel);
-        case 3: return launch_r<3, false>(a, batch, nullptr, s, box_kernel);
-        case 4: return launch_r<4, false>(a, batch, nullptr, s, box_kernel);
-        case 5: return launch_r<5, false>(a, batch, nullptr, s, box_kernel);
-        case 6: return launch_r<6, false>(a, batch, nullptr, s, box_kernel);
-        case 7: return launch_r<7, false>(a, batch, nullptr, s, box_kernel);
-        case 8: return launch_r<8, false>(a, batch, nullptr, s, box_kernel);
-        case 9: return launch_r<9, false>(a, batch, nullptr, s, box_kernel);
-        case 10: return launch_r<10, false>(a, batch, nullptr, s, box_kernel);
-        case 11: return launch_r<11, false>(a, batch, nullptr, s, box_kernel);
-        case 12: return launch_r<12, false>(a, batch, nullptr, s, box_kernel);
-        case 13: return launch_r<13, false>(a, batch, nullptr, s, box_kernel);
-        case 14: return launch_r<14, false>(a, batch, nullptr, s, box_kernel);
-        case 15: return launch_r<15, false>(a, batch, nullptr, s, box_kernel);
+        case 0: return launch_r<0, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 1: return launch_r<1, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 2: return launch_r<2, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 3: return launch_r<3, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 4: return launch_r<4, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 5: return launch_r<5, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 6: return launch_r<6, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 7: return launch_r<7, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 8: return launch_r<8, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 9: return launch_r<9, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 10: return launch_r<10, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 11: return launch_r<11, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 12: return launch_r<12, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 13: return launch_r<13, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 14: return launch_r<14, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        case 15: return launch_r<15, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
         default: return launch_box_match_generic(a, batch, s);
     }
 }

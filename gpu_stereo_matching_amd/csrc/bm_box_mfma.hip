@@ -1,5 +1,5 @@
 // bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
-// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22).
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22, §24).
 //
 // Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
 //
@@ -9,6 +9,8 @@
 // one L read, two R reads, v_min3_u32 on the two keys of a pixel.  Each wave keeps its best keys for the whole
 // tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
+// A workgroup walks a contiguous range of tiles; along a row of tiles it keeps the right band in LDS and stages
+// only the new columns.
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -31,6 +33,7 @@
 // the order (4g + j, 16 + 4g + j), and the constant horizontal band (the A operand) is built in that order.
 // R sits in LDS column-major ([column][64 rows] f16, 128 B per column, 16-B row groups XOR-swizzled by the
 // column), so a lane's R operand for any d is one ds_read_b128 at column x - d.
+#include <atomic>
 #include <type_traits>
 
 #include "bm_common.h"
@@ -66,10 +69,19 @@ struct MG {
     static constexpr int RC = kT + DMAX;                           // staged right-band columns
     static constexpr int RS_BYTES = RC * kColB;
     static constexpr int L_BYTES = kT * kColB;
-    static constexpr int LDS_BYTES = RS_BYTES + L_BYTES;
+    static constexpr int LDS_BYTES = L_BYTES + RS_BYTES;           // the left tile first, then the right band
     static constexpr int BIAS = ((2 * R + 1) * 255 + 1) / 2;
+    // A workgroup that goes on to the tile to the right keeps the RC - TOX band columns both tiles share: it moves
+    // them down by TOX columns and stages the TOX new ones, as whole 4-column groups from column NEW0 on (the group
+    // that straddles RC - TOX restages up to three moved columns with the values they already hold)
+    static constexpr int KEEP = RC - TOX;
+    static constexpr int NEW0 = KEEP & ~3;
+    static constexpr int NEW4 = (RC - NEW0) / 4;                   // 4-column groups staged for a carried band
+    static constexpr int MOVE_U = (KEEP * 8 + kThreads - 1) / kThreads;   // 16-B units per thread of the move
     static_assert(TOY + 2 * R <= kT && TOX + 2 * R <= kT, "every output's window lies in the input tile");
-    static_assert(TOY * FOLD * 4 <= LDS_BYTES, "the fold plane aliases the staged tiles");
+    static_assert(8 * NEW4 + 8 * (kT / 4) <= kThreads, "a carried tile stages in one pass");
+    static_assert(TOY * FOLD * 4 <= L_BYTES + TOX * kColB,
+                  "the fold plane aliases the left tile and the band columns the next tile drops, none it keeps");
     static_assert(BIAS < 2048 && (2 * R + 1) * 255 - BIAS < 2048, "D1 exact in f16");
     static_assert((int64_t)(2 * R + 1) * (2 * R + 1) * 255 * 256 + 255 < (1 << 24), "keys exact in f32");
 };
@@ -93,7 +105,19 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p, int y, int x, int W
     return v;
 }
 
-// stage 4 * NC4 columns x 64 rows of `img` from (ytop, xleft) as f16 1024 + v, column-major
+// eight rows of one element (4 columns x 8 rows) as f16 1024 + v into columns `col`.. of row group q
+__device__ __forceinline__ void stage_pack(const uint32_t (&w)[8], uint8_t* dst, int col, int q) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        u4 v;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            v[m] = 0x64006400u | ((w[2 * m] >> (8 * b)) & 0xFFu) | (((w[2 * m + 1] >> (8 * b)) & 0xFFu) << 16);
+        *reinterpret_cast<u4*>(dst + slot(col + b, q)) = v;
+    }
+}
+
+// stage 4 * NC4 columns x 64 rows of `img` from (ytop, xleft), column-major
 template <int NC4>
 __device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xleft, int W, int H, int pitch,
                                            uint8_t* dst, int tid) {
@@ -102,15 +126,33 @@ __device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xle
         uint32_t w[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) w[i] = ld_u32(img, ytop + 8 * q + i, xleft + 4 * j, W, H, pitch);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            u4 v;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                v[m] = 0x64006400u | ((w[2 * m] >> (8 * b)) & 0xFFu) | (((w[2 * m + 1] >> (8 * b)) & 0xFFu) << 16);
-            *reinterpret_cast<u4*>(dst + slot(4 * j + b, q)) = v;
-        }
+        stage_pack(w, dst, 4 * j, q);
     }
+}
+
+// A carried tile stages in one pass, one element per thread: the NEW4 new groups of the right band (from staged
+// column NEW0) and the left tile.  Threads past the last element repeat it: no branch, the same bytes
+template <int NEW0, int NEW4>
+struct CarriedElem {
+    bool right;
+    int q, col, dx;   // row group, first staged column, image column offset from the piece's first
+    __device__ __forceinline__ explicit CarriedElem(int tid) {
+        constexpr int NR = 8 * NEW4, NL = 8 * (kT / 4);
+        const int e = min(tid, NR + NL - 1);
+        right = e < NR;
+        const int el = e - NR;
+        q = right ? e / NEW4 : el / (kT / 4);
+        dx = 4 * (right ? e - q * NEW4 : el - q * (kT / 4));
+        col = (right ? NEW0 : 0) + dx;
+    }
+};
+
+// The thread index as a value the compiler takes to change from tile to tile: what staging and the band move derive
+// from it (element indices, LDS slots) is then computed where it is used, not hoisted out of the tile loop and held
+// in registers over the disparity loop, which has none to spare (no instruction is emitted)
+__device__ __forceinline__ int per_tile(int tid) {
+    asm volatile("" : "+v"(tid));
+    return tid;
 }
 
 constexpr uint32_t kAbsBits = 0x7FFF7FFFu;
@@ -139,13 +181,15 @@ __device__ __forceinline__ f4 mfma(u4 a, u4 b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
 }
 
-template <int R, int DMAX, int NP>
-__global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int tiles_x, int tiles_y) {
+// WALK: the workgroup walks a range of tiles; false: one tile per workgroup, the tile loop and everything carried
+// compiled away
+template <int R, int DMAX, int NP, bool WALK>
+__device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, int tiles_y, int per, int rem) {
     using G = MG<R, DMAX, NP>;
     constexpr int NXB = G::NXB, NOB = G::NOB;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t* rsm = smem;                  // [RC][64] f16, swizzled
-    uint8_t* lsm = smem + G::RS_BYTES;    // [64][64] f16, swizzled
+    uint8_t* lsm = smem;                  // [64][64] f16, swizzled
+    uint8_t* rsm = smem + G::L_BYTES;     // [RC][64] f16, swizzled
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -153,24 +197,23 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const int l16 = lane & 15;
     const int g = lane >> 4;
 
+    // Workgroup position k of n walks the tiles [k T / n, (k + 1) T / n) of the sequence [frame][ty][tx]: with n = T
+    // one tile each; with fewer, runs along a row of tiles, whose right bands overlap.  T = per n + rem from the
+    // host, so k T / n = k per + k rem / n, and the 64-bit division is skipped where n divides T
+    const int wg = xcd_tile(blockIdx.x, gridDim.x);
+    int t_begin = wg * per, t_end = t_begin + per;
+    if (WALK && rem != 0) {
+        t_begin += (int)((int64_t)wg * rem / (int)gridDim.x);
+        t_end += (int)((int64_t)(wg + 1) * rem / (int)gridDim.x);
+    }
+    if constexpr (!WALK) t_end = t_begin + 1;
+    if (t_begin >= t_end) return;
     const int tiles = tiles_x * tiles_y;
-    const int tile_id = xcd_tile(blockIdx.x, gridDim.x);   // [frame][ty][tx]
-    const int frame = tile_id / tiles;
-    const int t = tile_id - frame * tiles;
-    const int ty = t / tiles_x;
-    const int tx = t - ty * tiles_x;
-    const int x0 = tx * G::TOX;
-    const int y0 = ty * G::TOY;
+    int frame = t_begin / tiles;
+    int ty = (t_begin - frame * tiles) / tiles_x;
+    int tx = t_begin - frame * tiles - ty * tiles_x;
     const int W = a.W, H = a.H;
     const int d_lo = a.d_lo, d_hi = a.d_hi;
-
-    const uint8_t* Lf = a.left + (int64_t)frame * a.frame_stride;
-    const uint8_t* Rf = a.right + (int64_t)frame * a.frame_stride;
-
-    // staged right column k is image column band0 + k: pixel column c at disparity d reads k = c - d - band0
-    const int band0 = x0 - R - d_lo - DMAX;
-    stage_cols<G::RC / 4>(Rf, y0 - R, band0, W, H, a.pitch, rsm, tid);
-    stage_cols<kT / 4>(Lf, y0 - R, x0 - R, W, H, a.pitch, lsm, tid);
 
     // ---- constant bands ----
     // vertical (B operand of stage 1): element j is input row k = 8g + j of a 32-row chunk against output row
@@ -205,210 +248,346 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int 
     const f4 c1 = {nbias, nbias, nbias, nbias};
     const float c2base = (float)(256 * (2 * R + 1) * G::BIAS);
 
-    // best keys as f32 bit patterns: [output row block][output column block][column 4g + i], row l16
-    uint32_t best[NOB][NXB][4];
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-        for (int xb = 0; xb < NXB; ++xb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) best[ob][xb][i] = kInfBits;
-
-    // disparities past W - x0 are invalid for every output of the tile (Device.cu:44's break)
-    const int d_end = min(d_hi, W - x0 + 1);
-    const int nd = max(d_end - d_lo, 0);
-    const int dw_lo = d_lo + (wave * nd) / kNW;
-    const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
-    // largest d valid for every output of the tile
-    const int d_free = W - (min(x0 + G::TOX, W) - 1);
-    // Both masks are monotone in d: a staged column c needs AD = 0 where c < d (from d = x0 - R + 1 on) or c >= W
-    // (every d), an output column x has no key where d > W - x (from d = d_free + 1 on).  d_m is the first
-    // disparity of the tile that needs either; each wave walks the whole passes below it in the unmasked loop and
-    // the rest of its range in a masked one
-    const int d_m = (x0 - R + kT > W) ? d_lo : max(min(x0 - R, d_free) + 1, d_lo);
-    const int n_free = max(min(dw_hi, d_m) - dw_lo, 0);
-    const int dw_m = dw_lo + n_free - n_free % NP;
-
     const int laddr = slot(l16, g);   // + 16 columns per block; chunk 1 is ^ 64
 
-    __syncthreads();
-
-    // one loop over [lo, hi); MASKED: with the c >= d and c < W mask of the staged columns and the d <= W - x mask of
-    // the outputs
-    auto run = [&](auto masked_c, const int lo, const int hi) {
-        constexpr bool MASKED = decltype(masked_c)::value;
-        // NP = 2: two disparities per pass; an odd range ends with its last d twice (the same keys: min3 is
-        // unchanged, and no column outside the loop's own range is read)
+    bool carried = false;   // the tile's band and left tile are in LDS already (the end of the previous tile)
 #pragma unroll 1
-        for (int d = lo; d < hi; d += NP) {
-            const int dd[2] = {d, min(d + 1, hi - 1)};
-            int raddr[NP];
-            float c2v[NP];
-            f4 c2[NP];
+    for (int tile = t_begin;; ++tile) {
+        const int x0 = tx * G::TOX;
+        const int y0 = ty * G::TOY;
+        const uint8_t* Lf = a.left + (int64_t)frame * a.frame_stride;
+        const uint8_t* Rf = a.right + (int64_t)frame * a.frame_stride;
+
+        // staged right column k is image column band0 + k: pixel column c at disparity d reads k = c - d - band0
+        if (!carried) {
+            const int band0 = x0 - R - d_lo - DMAX;
+            const int st = per_tile(tid);
+            stage_cols<G::RC / 4>(Rf, y0 - R, band0, W, H, a.pitch, rsm, st);
+            stage_cols<kT / 4>(Lf, y0 - R, x0 - R, W, H, a.pitch, lsm, st);
+        }
+
+        // best keys as f32 bit patterns: [output row block][output column block][column 4g + i], row l16
+        uint32_t best[NOB][NXB][4];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
-                c2v[p] = c2base + (float)dd[p];
-                c2[p] = f4{c2v[p], c2v[p], c2v[p], c2v[p]};
-            }
-            // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the d-dependent
-            // zero (d >= 0) keeps the reads inside the loop, once per pair
-            const int laddr_d = laddr + (int)((uint32_t)d >> 31);
-            // t[p][ob]: the packed D1 of two adjacent column blocks of disparity p, a stage-2 B operand.  Even blocks
-            // go to its low half and odd blocks to its high half, so no half is ever copied; bh or bhs matches the
-            // order.  With NXB = 4 the last output block (cb == 4) pairs block 3 with the stale block 2: with the
-            // left block in the high half the stale columns meet only outputs past TOX, which are never written
-            u4 t[NP][NOB];
+        for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-            for (int cb = 0; cb <= NXB; ++cb) {
-                if (cb < 4) {
-                    const u4 l0 = *reinterpret_cast<const u4*>(lsm + laddr_d + cb * 16 * kColB);
-                    const u4 l1 = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ 64) + cb * 16 * kColB);
+            for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr[p] + cb * 16 * kColB);
-                        const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ 64) + cb * 16 * kColB);
-                        // a lane is one image column for all eight AD registers: its mask rides on their AND
-                        uint32_t keep = kAbsBits;
-                        // (d <= c < W as one unsigned compare: d <= W in every pass.  The scalar part goes through
-                        // readfirstlane so that no per-lane part of it is hoisted and held over the loop)
-                        if constexpr (MASKED) {
-                            const int c0 = __builtin_amdgcn_readfirstlane(x0 - R + 16 * cb - dd[p]);
-                            keep = (uint32_t)(l16 + c0) < (uint32_t)(W - dd[p]) ? kAbsBits : 0u;
+                for (int i = 0; i < 4; ++i) best[ob][xb][i] = kInfBits;
+
+        // disparities past W - x0 are invalid for every output of the tile (Device.cu:44's break)
+        const int d_end = min(d_hi, W - x0 + 1);
+        const int nd = max(d_end - d_lo, 0);
+        const int dw_lo = d_lo + (wave * nd) / kNW;
+        const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
+        // largest d valid for every output of the tile
+        const int d_free = W - (min(x0 + G::TOX, W) - 1);
+        // Both masks are monotone in d: a staged column c needs AD = 0 where c < d (from d = x0 - R + 1 on) or c >= W
+        // (every d), an output column x has no key where d > W - x (from d = d_free + 1 on).  d_m is the first
+        // disparity of the tile that needs either; each wave walks the whole passes below it in the unmasked loop and
+        // the rest of its range in a masked one
+        const int d_m = (x0 - R + kT > W) ? d_lo : max(min(x0 - R, d_free) + 1, d_lo);
+        const int n_free = max(min(dw_hi, d_m) - dw_lo, 0);
+        const int dw_m = dw_lo + n_free - n_free % NP;
+
+        // Where the next tile of the range is the right-hand neighbour and its new band columns and left tile lie
+        // inside the image (uniform per tile), its eight staging loads are issued here, unconditional dword loads,
+        // and consumed after the fold: the disparity loop covers their latency
+        const bool carry_next = WALK && tile + 1 < t_end && tx + 1 < tiles_x;
+        const int nxl = x0 + G::TOX - R, nxr = nxl - d_lo - DMAX + G::NEW0;
+        const bool prefetch = carry_next && y0 - R >= 0 && y0 - R + kT <= H && nxr >= 0 && nxl + kT <= W;
+        uint32_t pw[8];
+        if (prefetch) {
+            const CarriedElem<G::NEW0, G::NEW4> ce(per_tile(tid));
+            const uint8_t* p = (ce.right ? Rf : Lf) + (int64_t)(y0 - R + 8 * ce.q) * a.pitch +
+                               ((ce.right ? nxr : nxl) + ce.dx);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)i * a.pitch, 4);
+        }
+
+        __syncthreads();
+
+        // one loop over [lo, hi); MASKED: with the c >= d and c < W mask of the staged columns and the d <= W - x
+        // mask of the outputs
+        auto run = [&](auto masked_c, const int lo, const int hi) {
+            constexpr bool MASKED = decltype(masked_c)::value;
+            // NP = 2: two disparities per pass; an odd range ends with its last d twice (the same keys: min3 is
+            // unchanged, and no column outside the loop's own range is read)
+#pragma unroll 1
+            for (int d = lo; d < hi; d += NP) {
+                const int dd[2] = {d, min(d + 1, hi - 1)};
+                int raddr[NP];
+                float c2v[NP];
+                f4 c2[NP];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
+                    c2v[p] = c2base + (float)dd[p];
+                    c2[p] = f4{c2v[p], c2v[p], c2v[p], c2v[p]};
+                }
+                // L does not depend on d, but holding it would take 32 more registers and a wave per SIMD: the
+                // d-dependent zero (d >= 0) keeps the reads inside the loop, once per pair
+                const int laddr_d = laddr + (int)((uint32_t)d >> 31);
+                // t[p][ob]: the packed D1 of two adjacent column blocks of disparity p, a stage-2 B operand.  Even
+                // blocks go to its low half and odd blocks to its high half, so no half is ever copied; bh or bhs
+                // matches the order.  With NXB = 4 the last output block (cb == 4) pairs block 3 with the stale block
+                // 2: with the left block in the high half the stale columns meet only outputs past TOX, which are
+                // never written
+                u4 t[NP][NOB];
+#pragma unroll
+                for (int cb = 0; cb <= NXB; ++cb) {
+                    if (cb < 4) {
+                        const u4 l0 = *reinterpret_cast<const u4*>(lsm + laddr_d + cb * 16 * kColB);
+                        const u4 l1 = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ 64) + cb * 16 * kColB);
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            const u4 r0 = *reinterpret_cast<const u4*>(rsm + raddr[p] + cb * 16 * kColB);
+                            const u4 r1 = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ 64) + cb * 16 * kColB);
+                            // a lane is one image column for all eight AD registers: its mask rides on their AND
+                            uint32_t keep = kAbsBits;
+                            // (d <= c < W as one unsigned compare: d <= W in every pass.  The scalar part goes through
+                            // readfirstlane so that no per-lane part of it is hoisted and held over the loop)
+                            if constexpr (MASKED) {
+                                const int c0 = __builtin_amdgcn_readfirstlane(x0 - R + 16 * cb - dd[p]);
+                                keep = (uint32_t)(l16 + c0) < (uint32_t)(W - dd[p]) ? kAbsBits : 0u;
+                            }
+                            const u4 ad0 = abs_diff(l0, r0, keep);
+                            const u4 ad1 = abs_diff(l1, r1, keep);
+                            // output row blocks 0..NOB-1 of this column block from the two 32-row chunks
+                            f4 sv[4];
+                            sv[0] = mfma(ad0, bv0, c1);
+                            sv[1] = mfma(ad0, bvm, c1);
+                            sv[1] = mfma(ad1, bvp, sv[1]);
+                            sv[2] = mfma(ad1, bv0, c1);
+                            if constexpr (NOB == 4) sv[3] = mfma(ad1, bvm, c1);
+#pragma unroll
+                            for (int ob = 0; ob < NOB; ++ob) {
+                                const uint2 pk = pack_f16(sv[ob]);
+                                t[p][ob][2 * (cb & 1)] = pk.x;
+                                t[p][ob][2 * (cb & 1) + 1] = pk.y;
+                            }
                         }
-                        const u4 ad0 = abs_diff(l0, r0, keep);
-                        const u4 ad1 = abs_diff(l1, r1, keep);
-                        // output row blocks 0..NOB-1 of this column block from the two 32-row chunks
-                        f4 sv[4];
-                        sv[0] = mfma(ad0, bv0, c1);
-                        sv[1] = mfma(ad0, bvm, c1);
-                        sv[1] = mfma(ad1, bvp, sv[1]);
-                        sv[2] = mfma(ad1, bv0, c1);
-                        if constexpr (NOB == 4) sv[3] = mfma(ad1, bvm, c1);
+                    }
+                    // NP = 2: the scheduler takes stage 1 and stage 2 of a column block as regions of their own: over
+                    // the whole pass its latency-hiding order needs more than 168 registers and it falls back to source
+                    // order (65 s_nop per pass instead of 20)
+                    if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
+                    if (cb >= 1) {
+                        const int xb = cb - 1;
+                        // an output column past W - d starts from +inf: the products are finite, so its accumulator
+                        // stays +inf (kInfBits exactly) for every row block, and the min and the epilogue read it as
+                        // "no valid d".  Built per column block, so it is not held over the pass
+                        f4 c2x[NP];
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            c2x[p] = c2[p];
+                            if constexpr (MASKED) {
+                                // element i is output column x0 + 16 xb + 4g + i, valid for d <= W - x.  No scalar skip
+                                // of blocks that are valid throughout: a branch inside the pass spills
+                                const int e = __builtin_amdgcn_readfirstlane(W - x0 - 16 * xb - dd[p]) - 4 * g;
+#pragma unroll
+                                for (int i = 0; i < 4; ++i)
+                                    c2x[p][i] = i <= e ? c2v[p] : __builtin_bit_cast(float, kInfBits);
+                            }
+                        }
 #pragma unroll
                         for (int ob = 0; ob < NOB; ++ob) {
-                            const uint2 pk = pack_f16(sv[ob]);
-                            t[p][ob][2 * (cb & 1)] = pk.x;
-                            t[p][ob][2 * (cb & 1) + 1] = pk.y;
+                            u4 o[NP];
+#pragma unroll
+                            for (int p = 0; p < NP; ++p)
+                                o[p] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2x[p]));
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                uint32_t k = o[0][i];
+#pragma unroll
+                                for (int p = 1; p < NP; ++p) k = min(k, o[p][i]);
+                                best[ob][xb][i] = min(best[ob][xb][i], k);   // NP = 2: v_min3_u32
+                            }
                         }
                     }
+                    if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
                 }
-                // NP = 2: the scheduler takes stage 1 and stage 2 of a column block as regions of their own: over the
-                // whole pass its latency-hiding order needs more than 168 registers and it falls back to source order
-                // (65 s_nop per pass instead of 20)
-                if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
-                if (cb >= 1) {
-                    const int xb = cb - 1;
-                    // an output column past W - d starts from +inf: the products are finite, so its accumulator
-                    // stays +inf (kInfBits exactly) for every row block, and the min and the epilogue read it as
-                    // "no valid d".  Built per column block, so it is not held over the pass
-                    f4 c2x[NP];
+            }
+        };
+        run(std::false_type{}, dw_lo, dw_m);
+        run(std::true_type{}, dw_m, dw_hi);
+
+        __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
+
+        // ---- fold the waves (same lane = same pixels in every wave) through one LDS plane ----
+        uint32_t* fold = reinterpret_cast<uint32_t*>(smem);   // [TOY][FOLD] f32 bit patterns
+        if (wave == 0) {
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        c2x[p] = c2[p];
-                        if constexpr (MASKED) {
-                            // element i is output column x0 + 16 xb + 4g + i, valid for d <= W - x.  No scalar skip
-                            // of blocks that are valid throughout: a branch inside the pass spills
-                            const int e = __builtin_amdgcn_readfirstlane(W - x0 - 16 * xb - dd[p]) - 4 * g;
+            for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                c2x[p][i] = i <= e ? c2v[p] : __builtin_bit_cast(float, kInfBits);
-                        }
-                    }
+                for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
-                    for (int ob = 0; ob < NOB; ++ob) {
-                        u4 o[NP];
+                    for (int i = 0; i < 4; ++i)
+                        fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i] = best[ob][xb][i];
+        }
+        __syncthreads();
+        if (wave != 0) {
 #pragma unroll
-                        for (int p = 0; p < NP; ++p)
-                            o[p] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2x[p]));
+            for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            uint32_t k = o[0][i];
+                for (int xb = 0; xb < NXB; ++xb)
 #pragma unroll
-                            for (int p = 1; p < NP; ++p) k = min(k, o[p][i]);
-                            best[ob][xb][i] = min(best[ob][xb][i], k);   // NP = 2: v_min3_u32
-                        }
-                    }
-                }
-                if constexpr (NP == 2) __builtin_amdgcn_sched_barrier(0);
+                    for (int i = 0; i < 4; ++i)
+                        atomicMin(&fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i], best[ob][xb][i]);
+        }
+        __syncthreads();
+        uint8_t* Df = a.disp ? a.disp + (int64_t)frame * a.out_frame_stride : nullptr;
+        uint32_t* Kf = a.keys ? a.keys + (int64_t)frame * W * H : nullptr;
+        // lane = output column, rows over the waves
+        if (lane < G::TOX && x0 + lane < W) {
+            const int ylim = min(G::TOY, H - y0);
+            uint8_t* drow = Df ? Df + (int64_t)y0 * a.out_pitch + x0 + lane : nullptr;
+            uint32_t* krow = Kf ? Kf + (int64_t)y0 * W + x0 + lane : nullptr;
+            for (int j = wave; j < ylim; j += kNW) {
+                // the f32 key to its integer (+inf: no valid d), then the seed
+                const uint32_t kb = fold[j * G::FOLD + lane];
+                const uint32_t kf = kb >= kInfBits ? 0xFFFFFFFFu : (uint32_t)__builtin_bit_cast(float, kb);
+                const uint32_t k = min(kf, a.seed_key);
+                if (drow) drow[(int64_t)j * a.out_pitch] = k < a.thresh_key ? (uint8_t)(k & 0xFFu) : (uint8_t)0;
+                if (krow) krow[(int64_t)j * W] = k;
             }
         }
-    };
-    run(std::false_type{}, dw_lo, dw_m);
-    run(std::true_type{}, dw_m, dw_hi);
 
-    __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
-
-    // ---- fold the waves (same lane = same pixels in every wave) through one LDS plane ----
-    uint32_t* fold = reinterpret_cast<uint32_t*>(smem);   // [TOY][FOLD] f32 bit patterns
-    if (wave == 0) {
-#pragma unroll
-        for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-            for (int xb = 0; xb < NXB; ++xb)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i] = best[ob][xb][i];
-    }
-    __syncthreads();
-    if (wave != 0) {
-#pragma unroll
-        for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-            for (int xb = 0; xb < NXB; ++xb)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    atomicMin(&fold[(16 * ob + l16) * G::FOLD + 16 * xb + 4 * g + i], best[ob][xb][i]);
-    }
-    __syncthreads();
-    uint8_t* Df = a.disp ? a.disp + (int64_t)frame * a.out_frame_stride : nullptr;
-    uint32_t* Kf = a.keys ? a.keys + (int64_t)frame * W * H : nullptr;
-    // lane = output column, rows over the waves
-    if (lane < G::TOX && x0 + lane < W) {
-        const int ylim = min(G::TOY, H - y0);
-        uint8_t* drow = Df ? Df + (int64_t)y0 * a.out_pitch + x0 + lane : nullptr;
-        uint32_t* krow = Kf ? Kf + (int64_t)y0 * W + x0 + lane : nullptr;
-        for (int j = wave; j < ylim; j += kNW) {
-            // the f32 key to its integer (+inf: no valid d), then the seed
-            const uint32_t kb = fold[j * G::FOLD + lane];
-            const uint32_t kf = kb >= kInfBits ? 0xFFFFFFFFu : (uint32_t)__builtin_bit_cast(float, kb);
-            const uint32_t k = min(kf, a.seed_key);
-            if (drow) drow[(int64_t)j * a.out_pitch] = k < a.thresh_key ? (uint8_t)(k & 0xFFu) : (uint8_t)0;
-            if (krow) krow[(int64_t)j * W] = k;
+        // ---- the next tile of the range ----
+        if (tile + 1 == t_end) break;
+        carried = carry_next;
+        if (++tx == tiles_x) {
+            tx = 0;
+            if (++ty == tiles_y) {
+                ty = 0;
+                ++frame;
+            }
         }
+        if (!carried) {
+            __syncthreads();   // the fold plane is read: the next tile stages over it
+            continue;
+        }
+        // The right-hand neighbour: its band is this one moved down by TOX columns (best[] is dead: through registers,
+        // each side with its own swizzle, since the shift changes (col >> 1) & 7), and TOX new columns.  The kept
+        // columns lie past the fold plane.  Threads past the last 16-B unit repeat it: no branch, the same bytes
+        const int mt = per_tile(tid);
+        u4 mv[G::MOVE_U];
+#pragma unroll
+        for (int i = 0; i < G::MOVE_U; ++i) {
+            const int u = min(mt + i * kThreads, G::KEEP * 8 - 1);
+            mv[i] = *reinterpret_cast<const u4*>(rsm + slot((u >> 3) + G::TOX, u & 7));
+        }
+        __syncthreads();   // the band and the fold plane are read
+#pragma unroll
+        for (int i = 0; i < G::MOVE_U; ++i) {
+            const int u = min(mt + i * kThreads, G::KEEP * 8 - 1);
+            *reinterpret_cast<u4*>(rsm + slot(u >> 3, u & 7)) = mv[i];
+        }
+        const CarriedElem<G::NEW0, G::NEW4> ce(mt);
+        if (!prefetch) {   // an edge tile: the guarded loads, now
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                pw[i] = ld_u32(ce.right ? Rf : Lf, y0 - R + 8 * ce.q + i, (ce.right ? nxr : nxl) + ce.dx, W, H,
+                               a.pitch);
+        }
+        stage_pack(pw, ce.right ? rsm : lsm, ce.col, ce.q);
     }
 }
 
 template <int R, int DMAX, int NP>
-hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s) {
+__global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int tiles_x, int tiles_y, int per,
+                                                                int rem) {
+    box_mfma_tiles<R, DMAX, NP, true>(a, tiles_x, tiles_y, per, rem);
+}
+
+// One d per pass, one tile per workgroup (what auto launches at NP = 1): with the tile loop around it the NP = 1
+// disparity loop loses the scheduler's order (42 s_nop per pass instead of 4) whatever its register count
+template <int R, int DMAX>
+__global__ __launch_bounds__(kThreads, 3) void box_mfma_tile_kernel(MatchArgs a, int tiles_x, int tiles_y) {
+    box_mfma_tiles<R, DMAX, 1, false>(a, tiles_x, tiles_y, 1, 0);
+}
+
+constexpr int kMaxDevices = 64;
+// Workgroups launched per resident slot in auto mode.  One per slot is the slowest form (1080p D = 128 r = 5 x 128
+// frames: 5.40 ms against 5.07 for one tile per workgroup): the three waves of a SIMD keep their age order for the
+// whole launch and the launch ends with the youngest.  Shorter ranges let the dispatcher even that out: 2 / 4 / 8 / 16
+// per slot 5.14 / 4.94 / 4.98 / 4.94 ms, D = 256 x 32 frames 2.48 / 2.42 / 2.39 / 2.39
+// (profiles/microbench/box_mfma_rows_ab.txt)
+constexpr int kRangesPerSlot = 16;
+
+// workgroups of this instantiation the current device holds at once: the occupancy query times its CUs, asked once
+// per device and instantiation
+template <int R, int DMAX, int NP>
+hipError_t resident_workgroups(int* out) {
+    static std::atomic<int> slots[kMaxDevices];   // 0: not asked yet
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool cached = dev >= 0 && dev < kMaxDevices;
+    int v = cached ? slots[dev].load(std::memory_order_relaxed) : 0;
+    if (v == 0) {
+        int per_cu = 0, cus = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, box_mfma_kernel<R, DMAX, NP>, kThreads,
+                                                         (size_t)MG<R, DMAX, NP>::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+        v = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+        if (cached) slots[dev].store(v, std::memory_order_relaxed);
+    }
+    *out = v;
+    return hipSuccess;
+}
+
+// workgroups: 0 auto (kRangesPerSlot ranges of tiles per resident workgroup slot), n >= 1 that many, at most one
+// per tile
+template <int R, int DMAX, int NP>
+hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
     using G = MG<R, DMAX, NP>;
     const int tiles_x = (a.W + G::TOX - 1) / G::TOX;
     const int tiles_y = (a.H + G::TOY - 1) / G::TOY;
-    const int64_t blocks = (int64_t)tiles_x * tiles_y * batch;
-    if (blocks <= 0 || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((box_mfma_kernel<R, DMAX, NP>), dim3((unsigned)blocks), dim3(kThreads), (size_t)G::LDS_BYTES, s,
-                       a, tiles_x, tiles_y);
+    const int64_t total = (int64_t)tiles_x * tiles_y * batch;
+    if (total <= 0 || total > 0x7FFFFFFF || workgroups < 0) return hipErrorInvalidValue;
+    int64_t n = workgroups;
+    // one d per pass (short ranges at r <= 2): a tile's loop is too short to pay for the move and its barrier, auto
+    // keeps one tile per workgroup (1080p D = 32 r = 2 x 32 frames: 0.405 ms against 0.509 with ranges)
+    if constexpr (NP == 1) {
+        if (n == 0 || n >= total) {
+            hipLaunchKernelGGL((box_mfma_tile_kernel<R, DMAX>), dim3((unsigned)total), dim3(kThreads),
+                               (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
+            return hipGetLastError();
+        }
+    }
+    if (n == 0) {
+        int slots = 0;
+        hipError_t e = resident_workgroups<R, DMAX, NP>(&slots);
+        if (e != hipSuccess) return e;
+        n = (int64_t)slots * kRangesPerSlot;
+    }
+    if (n > total) n = total;
+    hipLaunchKernelGGL((box_mfma_kernel<R, DMAX, NP>), dim3((unsigned)n), dim3(kThreads), (size_t)G::LDS_BYTES, s, a,
+                       tiles_x, tiles_y, (int)(total / n), (int)(total % n));
     return hipGetLastError();
 }
 
 template <int R, int DMAX>
-hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s) {
+hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
     // short ranges at r <= 2 keep one d per pass on 62- / 60-row tiles: 1080p x 32 frames, D = 8 r = 1 0.206 against
     // 0.221 ms, D = 32 r = 2 0.396 against 0.404; from r = 3 or D = 48 on the paired loop is level or ahead
     // (profiles/microbench/box_mfma_pairs_ab.txt)
     if constexpr (DMAX == 64 && R <= 2) {
-        if (a.d_hi - a.d_lo <= 32) return launch_rdp<R, DMAX, 1>(a, batch, s);
+        if (a.d_hi - a.d_lo <= 32) return launch_rdp<R, DMAX, 1>(a, batch, s, workgroups);
     }
-    return launch_rdp<R, DMAX, 2>(a, batch, s);
+    return launch_rdp<R, DMAX, 2>(a, batch, s, workgroups);
 }
 
 template <int R>
-hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s) {
+hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
     const int dspan = a.d_hi - a.d_lo;
-    if (dspan <= 64) return launch_rd<R, 64>(a, batch, s);
-    if (dspan <= 128) return launch_rd<R, 128>(a, batch, s);
-    if (dspan <= 192) return launch_rd<R, 192>(a, batch, s);
-    return launch_rd<R, 256>(a, batch, s);
+    if (dspan <= 64) return launch_rd<R, 64>(a, batch, s, workgroups);
+    if (dspan <= 128) return launch_rd<R, 128>(a, batch, s, workgroups);
+    if (dspan <= 192) return launch_rd<R, 192>(a, batch, s, workgroups);
+    return launch_rd<R, 256>(a, batch, s, workgroups);
 }
 
 }  // namespace
@@ -418,16 +597,16 @@ bool box_mfma_scope(const MatchArgs& a) {
            a.d_hi <= kMaxDisp;
 }
 
-hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s) {
+hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
     if (!box_mfma_scope(a)) return hipErrorInvalidValue;
     switch (a.radius) {
-        case 1: return launch_r<1>(a, batch, s);
-        case 2: return launch_r<2>(a, batch, s);
-        case 3: return launch_r<3>(a, batch, s);
-        case 4: return launch_r<4>(a, batch, s);
-        case 5: return launch_r<5>(a, batch, s);
-        case 6: return launch_r<6>(a, batch, s);
-        case 7: return launch_r<7>(a, batch, s);
+        case 1: return launch_r<1>(a, batch, s, workgroups);
+        case 2: return launch_r<2>(a, batch, s, workgroups);
+        case 3: return launch_r<3>(a, batch, s, workgroups);
+        case 4: return launch_r<4>(a, batch, s, workgroups);
+        case 5: return launch_r<5>(a, batch, s, workgroups);
+        case 6: return launch_r<6>(a, batch, s, workgroups);
+        case 7: return launch_r<7>(a, batch, s, workgroups);
         default: return hipErrorInvalidValue;
     }
 }

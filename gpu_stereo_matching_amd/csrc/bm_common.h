@@ -42,11 +42,13 @@ constexpr int kMaxBoxRadius = 15;
 // Host-side launchers (bm_box.hip, bm_aux.hip).
 // box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the VALU kernels of bm_box.hip, 2 the matrix-pipe kernel
 // (bm_box_mfma.hip) wherever box_mfma_scope holds
-hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel = 0);
+// box_workgroups (SM_PARAM_BOX_WORKGROUPS): workgroups of a matrix-pipe launch, each walking a contiguous range of
+// tiles: 0 auto, n >= 1 that many (at most one per tile)
+hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel = 0, int box_workgroups = 0);
 // the plain box pass with both window sums on the matrix pipe: radius 1..kMaxFastRadius, valid_mode 0, no right
 // view; bit-exact with launch_box_match.  hipErrorInvalidValue outside box_mfma_scope
 bool box_mfma_scope(const MatchArgs& a);
-hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s);
+hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups = 0);
 hipError_t launch_box_match_generic(const MatchArgs& a, int batch, hipStream_t s);
 // Box matching + right view (+ LR check) in two launches (radius <= kMaxBoxRadius, d_lo == 0).
 // check = 1: a.disp receives the checked left disparity, right_out/mask_out (optional) dR and the

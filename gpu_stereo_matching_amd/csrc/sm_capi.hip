@@ -291,7 +291,7 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         // mirrored right view below takes it too)
         SM_HIP(sm::launch_box_match_strip(a, batch, s));
     } else {
-        SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel));
+        SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel, h->box_workgroups));
     }
     if (med) SM_HIP(sm::launch_median(left_raw, W, H, W, P, batch, kMedianRadius, disp, opitch, ostride, s));
     if (!lr) return SM_OK;
@@ -564,6 +564,13 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         if (value != 0.f && value != 1.f && value != 2.f)
             return fail(SM_ERR_INVALID_ARG, "box kernel is 0 (auto), 1 (legacy) or 2 (matrix)");
         h->box_kernel = (int)value;
+        return SM_OK;
+    }
+    if (param == SM_PARAM_BOX_WORKGROUPS) {
+        // (the comparison also rejects NaN; floats above 2^24 are not every integer, and no launch has that many slots)
+        if (!(value >= 0.f) || value > 16777216.f || (float)(int)value != value)
+            return fail(SM_ERR_INVALID_ARG, "box workgroups must be an integer >= 0 (0 = auto)");
+        h->box_workgroups = (int)value;
         return SM_OK;
     }
     if (param == SM_PARAM_UNIQUENESS) {

@@ -60,7 +60,7 @@ int slice_keys_pass(WsScope& ws, sm_handle* h, const uint8_t* dL, const uint8_t*
         return SM_OK;
     }
     if (!rkeys) {
-        SM_HIP(sm::launch_box_match(a, 1, s, h->box_kernel));
+        SM_HIP(sm::launch_box_match(a, 1, s, h->box_kernel, h->box_workgroups));
         return SM_OK;
     }
     int rc = ws.get(h->rpart, sm::box_right_partial_bytes(W, H, radius, d_hi - d_lo, 1), &a.rpart);

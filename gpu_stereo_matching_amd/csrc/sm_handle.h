@@ -114,6 +114,7 @@ struct sm_handle {
     // (default: on once sm_last_stage_ms has been called on the handle, or when SM_VERBOSE is set)
     int stage_timing = 2;
     int box_kernel = 0;          // SM_PARAM_BOX_KERNEL: 0 auto, 1 VALU kernels, 2 matrix-pipe kernel
+    int box_workgroups = 0;      // SM_PARAM_BOX_WORKGROUPS: 0 auto, n >= 1 workgroups per matrix-pipe launch
     int uniqueness = 0;          // SM_PARAM_UNIQUENESS: 0 off, 1..99 the sub-pixel calls' uniqueness ratio
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the

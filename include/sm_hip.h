@@ -136,8 +136,13 @@ enum {
                                   The matrix-pipe kernel covers radius 1..7 without the fused right view: with
                                   SM_LR_CHECK, radius 0 or radius >= 8 the value 2 silently runs the VALU
                                   kernels.  Other values: SM_ERR_INVALID_ARG */
-    SM_PARAM_UNIQUENESS = 7    /* uniqueness ratio of the sub-pixel calls (sm_match_subpix_device and friends): an
+    SM_PARAM_UNIQUENESS = 7,   /* uniqueness ratio of the sub-pixel calls (sm_match_subpix_device and friends): an
                                   integer 0..99, 0 (default) = off.  Other values: SM_ERR_INVALID_ARG */
+    SM_PARAM_BOX_WORKGROUPS = 8 /* workgroups of a matrix-pipe box launch, each walking a contiguous range of tiles
+                                  and keeping the right band along a row of tiles: 0 (default) auto, 16 per
+                                  workgroup the device holds at once; an integer n >= 1 that many, at most one per
+                                  tile (n >= tiles: one tile per workgroup, nothing kept).  The maps and keys do not
+                                  depend on it; the VALU kernels ignore it.  Other values: SM_ERR_INVALID_ARG */
 };
 
 typedef struct sm_handle sm_handle;
