@@ -10,7 +10,8 @@
 // tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
 // A workgroup walks a contiguous range of tiles; along a row of tiles it keeps the right band in LDS and stages
-// only the new columns.
+// only the new columns.  The unmasked paired loop is written slot by slot, every MFMA between vector
+// work of its own wave (run_paired).
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -291,19 +292,25 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         const int dw_m = dw_lo + n_free - n_free % NP;
 
         // Where the next tile of the range is the right-hand neighbour and its new band columns and left tile lie
-        // inside the image (uniform per tile), its eight staging loads are issued here, unconditional dword loads,
-        // and consumed after the fold: the disparity loop covers their latency
+        // inside the image (uniform per tile), its eight staging loads are unconditional dword loads, issued early
+        // (issue_prefetch) and consumed after the fold
         const bool carry_next = WALK && tile + 1 < t_end && tx + 1 < tiles_x;
         const int nxl = x0 + G::TOX - R, nxr = nxl - d_lo - DMAX + G::NEW0;
         const bool prefetch = carry_next && y0 - R >= 0 && y0 - R + kT <= H && nxr >= 0 && nxl + kT <= W;
         uint32_t pw[8];
-        if (prefetch) {
-            const CarriedElem<G::NEW0, G::NEW4> ce(per_tile(tid));
-            const uint8_t* p = (ce.right ? Rf : Lf) + (int64_t)(y0 - R + 8 * ce.q) * a.pitch +
-                               ((ce.right ? nxr : nxl) + ce.dx);
+        auto issue_prefetch = [&] {
+            if (prefetch) {
+                const CarriedElem<G::NEW0, G::NEW4> ce(per_tile(tid));
+                const uint8_t* p = (ce.right ? Rf : Lf) + (int64_t)(y0 - R + 8 * ce.q) * a.pitch +
+                                   ((ce.right ? nxr : nxl) + ce.dx);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)i * a.pitch, 4);
-        }
+                for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)i * a.pitch, 4);
+            }
+        };
+        // NP = 1: before the disparity loops, which cover the latency.  NP = 2: after the unmasked loop, whose order
+        // needs the eight registers; the masked loop, the fold and the epilogue are between the loads
+        // and their use
+        if constexpr (NP == 1) issue_prefetch();
 
         __syncthreads();
 
@@ -409,7 +416,174 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                 }
             }
         };
-        run(std::false_type{}, dw_lo, dw_m);
+        // The unmasked loop of two disparities per pass, the same arithmetic as run() in an order that gives every
+        // MFMA vector work of its own wave that does not wait for it.  A column block is a sequence of
+        // slots, one MFMA and two to four vector instructions each, a scheduling barrier after every slot, so the source
+        // order is the machine order:
+        //   stage 1   the AD quads (4 v_pk_add_f16 + 4 v_and_b32) in the order (p0, chunk 0), (p1, chunk 0),
+        //             (p0, chunk 1), (p1, chunk 1): the row block that needs chunk 0 alone is summed first for both
+        //             disparities, so its converts, stage 2 and mins run under the rest.  A quad's two MFMAs issue
+        //             under the next quad, half a quad or more after its last AND; a convert follows the sum it reads
+        //             by three MFMAs
+        //   stage 2   of the output block to the left: its six MFMAs under the last converts and the mins of the rows
+        //             done; the mins of the middle row block wait for the first AD quad of the next column block
+        //   reads     chunk 0 of the next block goes out before the last three stage-2 MFMAs, chunk 1 with the
+        //             block's first quad (the R read its last quad needs one slot later), so only the first block of
+        //             a pass begins with a wait.  Reading all six ahead, or holding the next tile's staging loads
+        //             over this loop as NP = 1 does, does not fit in 168 registers
+        auto run_paired = [&](auto np_c, const int lo, const int hi) {
+            static_assert(decltype(np_c)::value == 2 && NOB == 3, "the paired loop");
+            auto slot_end = [] { __builtin_amdgcn_sched_barrier(0); };
+            // the two keys of a pixel against its best: v_min3_u32
+            auto mins = [&](int ob, int x, const u4& o0, const u4& o1) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) best[ob][x][i] = min(best[ob][x][i], min(o0[i], o1[i]));
+            };
+#pragma unroll 1
+            for (int d = lo; d < hi; d += 2) {
+                const int dd[2] = {d, min(d + 1, hi - 1)};
+                int raddr[2];
+                f4 c2[2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
+                    const float c2v = c2base + (float)dd[p];
+                    c2[p] = f4{c2v, c2v, c2v, c2v};
+                }
+                const int laddr_d = laddr + (int)((uint32_t)d >> 31);   // as in run(): L is read once per pair
+                u4 t[2][NOB];
+                u4 lq[2], rq[2][2];   // [chunk], [p][chunk] of the block whose reads are out
+                // the reads of 32-row chunk c of column block cb
+                auto fetch_l = [&](int cb, int c) {
+                    lq[c] = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ (64 * c)) + cb * 16 * kColB);
+                };
+                auto fetch_r = [&](int cb, int p, int c) {
+                    rq[p][c] = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ (64 * c)) + cb * 16 * kColB);
+                };
+                auto fetch = [&](int cb, int c) {
+                    fetch_l(cb, c);
+                    fetch_r(cb, 0, c);
+                    fetch_r(cb, 1, c);
+                };
+                fetch(0, 0);
+                u4 om[2];   // stage 2 of the middle row block, carried to the next column block's first quad
+#pragma unroll
+                for (int cb = 0; cb <= NXB; ++cb) {
+                    const bool s1 = cb < 4, s2 = cb >= 1;
+                    const int xb = cb - 1;
+                    u4 ad[2][2];   // [p][chunk]
+                    f4 sv[2][NOB];
+                    u4 o[2][NOB];
+                    // elements 2h, 2h + 1 of AD quad (p, chunk c)
+                    auto half = [&](int p, int c, int h) {
+#pragma unroll
+                        for (int m = 2 * h; m < 2 * h + 2; ++m) {
+                            const uint32_t lm = lq[c][m], rm = rq[p][c][m];
+                            const h2 df = __builtin_bit_cast(h2, lm) - __builtin_bit_cast(h2, rm);
+                            ad[p][c][m] = __builtin_bit_cast(uint32_t, df) & kAbsBits;
+                        }
+                    };
+                    auto cvt = [&](int p, int ob) {
+                        const uint2 pk = pack_f16(sv[p][ob]);
+                        t[p][ob][2 * (cb & 1)] = pk.x;
+                        t[p][ob][2 * (cb & 1) + 1] = pk.y;
+                    };
+                    auto stage2 = [&](int ob, int p) {
+                        o[p][ob] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2[p]));
+                    };
+                    if (s1) {
+                        fetch_l(cb, 1);
+                        fetch_r(cb, 0, 1);
+                        half(0, 0, 0);
+                        half(0, 0, 1);
+                        if (cb >= 2) mins(1, xb - 1, om[0], om[1]);
+                        slot_end();
+                        fetch_r(cb, 1, 1);
+                        sv[0][0] = mfma(ad[0][0], bv0, c1);
+                        half(1, 0, 0);
+                        slot_end();
+                        sv[0][1] = mfma(ad[0][0], bvm, c1);
+                        half(1, 0, 1);
+                        slot_end();
+                        half(0, 1, 0);
+                        slot_end();
+                        sv[1][0] = mfma(ad[1][0], bv0, c1);
+                        half(0, 1, 1);
+                        slot_end();
+                        sv[1][1] = mfma(ad[1][0], bvm, c1);
+                        half(1, 1, 0);
+                        slot_end();
+                        sv[0][2] = mfma(ad[0][1], bv0, c1);
+                        half(1, 1, 1);
+                        slot_end();
+                        sv[0][1] = mfma(ad[0][1], bvp, sv[0][1]);
+                        cvt(0, 0);
+                        slot_end();
+                        sv[1][2] = mfma(ad[1][1], bv0, c1);
+                        cvt(1, 0);
+                        slot_end();
+                        sv[1][1] = mfma(ad[1][1], bvp, sv[1][1]);
+                        cvt(0, 2);
+                        slot_end();
+                        if (s2) stage2(0, 0);
+                        cvt(0, 1);
+                        slot_end();
+                        if (s2) stage2(0, 1);
+                        cvt(1, 2);
+                        slot_end();
+                        if (s2) stage2(2, 0);
+                        cvt(1, 1);
+                        slot_end();
+                        if (cb + 1 < 4) fetch(cb + 1, 0);
+                        if (s2) {
+                            stage2(1, 0);
+                            slot_end();
+                            stage2(2, 1);
+                            mins(0, xb, o[0][0], o[1][0]);
+                            slot_end();
+                            stage2(1, 1);
+                            slot_end();
+                            mins(2, xb, o[0][2], o[1][2]);
+                            slot_end();
+                            om[0] = o[0][1];
+                            om[1] = o[1][1];
+                        }
+                    } else {
+                        // the last output block: both halves of t are there
+                        stage2(0, 0);
+                        stage2(0, 1);
+                        slot_end();
+                        stage2(2, 0);
+                        mins(1, xb - 1, om[0], om[1]);
+                        slot_end();
+                        stage2(2, 1);
+                        slot_end();
+                        stage2(1, 0);
+                        mins(0, xb, o[0][0], o[1][0]);
+                        slot_end();
+                        stage2(1, 1);
+                        slot_end();
+                        mins(2, xb, o[0][2], o[1][2]);
+                        slot_end();
+                        om[0] = o[0][1];
+                        om[1] = o[1][1];
+                    }
+                }
+                mins(1, NXB - 1, om[0], om[1]);
+                slot_end();
+            }
+        };
+        if constexpr (NP == 2) {
+            run_paired(std::integral_constant<int, NP>{}, dw_lo, dw_m);
+            // (zeros on the other path: an undefined value would be taken as last tile's and held over the loop)
+            if (!prefetch) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) pw[i] = 0;
+            }
+            issue_prefetch();
+        } else {
+            run(std::false_type{}, dw_lo, dw_m);
+        }
         run(std::true_type{}, dw_m, dw_hi);
 
         __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them

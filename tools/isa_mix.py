@@ -21,6 +21,8 @@ CVT = 3.9
 
 
 def weight(op, operands):
+    if op.startswith("v_mfma"):
+        return 8.0   # the vector-issue share of a 16-cycle v_mfma_f32_16x16x32_f16
     if op.startswith("v_cvt"):
         return CVT
     if op.startswith("v_cndmask"):
@@ -81,14 +83,20 @@ def hot_path(path, name, exclude_op="v_cmp_lt_i32_e64"):
         m = re.match(r"^\s+s_(cbranch_\w+|branch)\s+(\.LBB\S+)", ln)
         if m and m.group(2) in labels and labels[m.group(2)] < i:
             loops.append((labels[m.group(2)], i))
-    a, b = max(loops, key=lambda t: t[1] - t[0])
+    # the innermost loop with the most VALU instructions outside the excluded blocks (for box_mfma_kernel the masked
+    # loop is one block longer than the unmasked one and holds `exclude_op`: the unmasked loop is the hot path)
+    inner = [l for l in loops if not any(o != l and l[0] <= o[0] and o[1] <= l[1] for o in loops)]
     n, cyc, mix = 0, 0.0, collections.Counter()
-    for lab, cnt, c, ops in loop_blocks(lines, a, b):
-        if exclude_op in ops:
-            continue
-        n += cnt
-        cyc += c
-        mix += ops
+    for a, b in inner:
+        n1, cyc1, mix1 = 0, 0.0, collections.Counter()
+        for lab, cnt, c, ops in loop_blocks(lines, a, b):
+            if exclude_op in ops:
+                continue
+            n1 += cnt
+            cyc1 += c
+            mix1 += ops
+        if n1 > n:
+            n, cyc, mix = n1, cyc1, mix1
     return {"kernel": name, "valu_per_iteration": n, "issue_cycles_per_iteration": round(cyc, 1),
             "avg_cycles_per_valu": round(cyc / n, 4), "mix": dict(mix.most_common()),
             "excluded_blocks_with": exclude_op}
