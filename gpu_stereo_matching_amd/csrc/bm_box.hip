@@ -22,8 +22,7 @@
 //     (v_sad_u8 / v_sad_hi_u8); CS = T_i - T_{i-2R-1} (column window sums, two d per dword).
 //   Phase H (lane = row x half-row): running window sum along x over the packed pairs, keys
 //     (S << 8 | d) built with v_perm_b32, folded with v_min3_u32.
-#include <cstdlib>
-
+#include "bm_box_plan.h"
 #include "bm_common.h"
 
 namespace sm {
@@ -122,6 +121,9 @@ struct Geo {
         return j * RBW + RB_SKEW * (((j & 15) >> 1) + 8 * (j >> 4));
     }
     static_assert(kTileH == 32, "rb_row's skew covers two 16-row halves");
+    // what bm_box_plan.h sizes the right-key partials by
+    static_assert(kTileH == kBoxTileH && kChunk == kBoxChunk && TW == box_tile_width(R) && DMAX == box_dmax(DMAX) &&
+                      PWP == box_partial_pitch(R, DMAX), "box_right_partial_bytes follows this geometry");
 };
 
 // two right-view workgroups per CU at d_max 128 (8 waves) and 192 (6 waves), skewed rows included
@@ -612,49 +614,11 @@ struct RightOut {
     uint32_t* rkeys;  // slice mode: raw right keys [batch][H][W] instead of dR (check 0, right null)
 };
 
-int compute_units() {
-    static const int n = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        return cus;
-    }();
-    return n;
-}
-
-// SM_WIDE_TILES=0 keeps the 4-wave kernel for every launch (A/B timing)
-bool wide_tiles_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("SM_WIDE_TILES");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Launches of more tiles than CUs but at most SM_BOX_MID_MAX (default 8) tiles per CU (batch 1 of a
-// mid-size frame) take 8-wave tiles, the d pairs split over twice the waves: the last round of tiles
-// ends sooner.  Same box, device resident, batch 1 (profiles/microbench/r04_box_mid_tiles_latency.txt):
-// 960x540 D=128 47.5 -> 39.7 us, 320x240 D=32 16.7 -> 13.6, 1080p D=128 88.5 -> 86.3; maps identical.
-// SM_BOX_MID=0 (read once) keeps the 4-wave tiles (A/B).
-int mid_tiles_max() {
-    static const int v = [] {
-        const char* e = std::getenv("SM_BOX_MID");
-        if (e && e[0] == '0') return 0;
-        const char* m = std::getenv("SM_BOX_MID_MAX");
-        return m ? std::atoi(m) : 8;
-    }();
-    return v;
-}
-
-// SM_BOX_MFMA=0 (read once) keeps the VALU kernels for every launch in auto mode (A/B timing)
-bool box_mfma_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("SM_BOX_MFMA");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
+// Launches of more tiles than CUs but at most kMidTilesPerCu tiles per CU (batch 1 of a mid-size frame) take 8-wave
+// tiles, the d pairs split over twice the waves: the last round of tiles ends sooner.  Same box, device resident,
+// batch 1 (profiles/microbench/r04_box_mid_tiles_latency.txt): 960x540 D=128 47.5 -> 39.7 us, 320x240 D=32
+// 16.7 -> 13.6, 1080p D=128 88.5 -> 86.3; maps identical.
+constexpr int kMidTilesPerCu = 8;
 
 // box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the kernels of this file, 2 the matrix-pipe kernel
 // (bm_box_mfma.hip) at any launch size; outside that kernel's scope (the right view, r = 0, r > 7) 2 is 0
@@ -685,16 +649,16 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         const int npairs = ((a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1)) / 2;
         const bool mfma_ok = R >= 1 && R <= kMaxFastRadius && box_mfma_scope(a);
         if (mfma_ok && box_kernel == 2) return launch_box_match_mfma(a, batch, s, box_workgroups);
+        const int cus = device_cus();
+        const int64_t mid_blocks = (int64_t)kMidTilesPerCu * cus;
         if constexpr (!kWideR<R>) {
-            if (wide_tiles_enabled() && blocks <= compute_units() && npairs >= 2 * kWideTile) {
+            if (blocks <= cus && npairs >= 2 * kWideTile) {
                 using GW = Geo<R, DMAX, kWideTile>;
                 hipLaunchKernelGGL((box_match_kernel<R, DMAX, false, kWideTile>), dim3((unsigned)blocks),
                                    dim3(64 * kWideTile), (size_t)GW::LDS_BYTES, s, a, tiles_x, tiles_y);
                 return hipGetLastError();
             }
-        }
-        if constexpr (!kWideR<R>) {
-            if (mid_tiles_max() > 0 && blocks <= (int64_t)mid_tiles_max() * compute_units() && npairs >= 16) {
+            if (blocks <= mid_blocks && npairs >= 16) {
                 using GM = Geo<R, DMAX, 8>;
                 hipLaunchKernelGGL((box_match_kernel<R, DMAX, false, 8>), dim3((unsigned)blocks), dim3(64 * 8),
                                    (size_t)GM::LDS_BYTES, s, a, tiles_x, tiles_y);
@@ -705,9 +669,7 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         // kernel: 1080p D = 128 r = 5, 128 frames per launch, 6.91 -> 6.04 ms; D = 256 x 32 frames 3.51 -> 2.94;
         // 4K D = 192 x 8 frames 2.51 -> 2.10; batch 1 stays on the 8-wave tiles (0.070 against 0.071 ms)
         // (profiles/microbench/box_mfma_headline_ab.txt)
-        if (mfma_ok && box_kernel == 0 && box_mfma_enabled() &&
-            blocks > (int64_t)(mid_tiles_max() > 0 ? mid_tiles_max() : 8) * compute_units())
-            return launch_box_match_mfma(a, batch, s, box_workgroups);
+        if (mfma_ok && box_kernel == 0 && blocks > mid_blocks) return launch_box_match_mfma(a, batch, s, box_workgroups);
         hipLaunchKernelGGL((box_match_kernel<R, DMAX, false>), dim3((unsigned)blocks), dim3(64 * kWaves<false, R>),
                            (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
     }
@@ -717,24 +679,13 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
 template <int R, bool RIGHT>
 hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel = 0,
                     int box_workgroups = 0) {
-    const int dspan = (a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1);
-    if (dspan <= 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
-    if (dspan <= 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    const int dmax = box_dmax(a.d_hi - a.d_lo);
+    if (dmax == 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    if (dmax == 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
     // 192 (cfg5): the right band and the right-key rows sized for 192, not 256, keep the plain kernel
     // at 4 workgroups/CU and the right-view kernel at 2
-    if (dspan <= 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    if (dmax == 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
     return launch_rd<R, 256, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
-}
-
-template <int R>
-size_t partial_bytes_r(int W, int H, int D, int batch) {
-    const int dspan = (D + kChunk - 1) & ~(kChunk - 1);
-    const int dmax = dspan <= 64 ? 64 : (dspan <= 128 ? 128 : (dspan <= 192 ? 192 : 256));
-    const int TW = kCols - 2 * R;
-    const int PW = TW + dmax + 1;
-    const int PWP = (PW + 7 + 3) & ~3;   // Geo::PWP
-    const size_t tiles = (size_t)((W + TW - 1) / TW) * ((H + kTileH - 1) / kTileH);
-    return tiles * (size_t)batch * kTileH * PWP * 4;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -779,77 +730,22 @@ __global__ __launch_bounds__(256) void box_match_generic_kernel(MatchArgs a, int
 }  // namespace
 
 hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel, int box_workgroups) {
-    switch (a.radius) {
-        case 0: return launch_r<0, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 1: return launch_r<1, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 2: return launch_r<2, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 3: return launch_r<3, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 4: return launch_r<4, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 5: return launch_r<5, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 6: return launch_r<6, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 7: return launch_r<7, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 8: return launch_r<8, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 9: return launch_r<9, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 10: return launch_r<10, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 11: return launch_r<11, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 12: return launch_r<12, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 13: return launch_r<13, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 14: return launch_r<14, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        case 15: return launch_r<15, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
-        default: return launch_box_match_generic(a, batch, s);
-    }
+    return with_radius<0, kMaxBoxRadius>(a.radius, hipErrorInvalidValue, [&](auto r) {
+        return launch_r<decltype(r)::value, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+    });
 }
 
-size_t box_right_partial_bytes(int W, int H, int radius, int D, int batch) {
-    switch (radius) {
-        case 0: return partial_bytes_r<0>(W, H, D, batch);
-        case 1: return partial_bytes_r<1>(W, H, D, batch);
-        case 2: return partial_bytes_r<2>(W, H, D, batch);
-        case 3: return partial_bytes_r<3>(W, H, D, batch);
-        case 4: return partial_bytes_r<4>(W, H, D, batch);
-        case 5: return partial_bytes_r<5>(W, H, D, batch);
-        case 6: return partial_bytes_r<6>(W, H, D, batch);
-        case 7: return partial_bytes_r<7>(W, H, D, batch);
-        case 8: return partial_bytes_r<8>(W, H, D, batch);
-        case 9: return partial_bytes_r<9>(W, H, D, batch);
-        case 10: return partial_bytes_r<10>(W, H, D, batch);
-        case 11: return partial_bytes_r<11>(W, H, D, batch);
-        case 12: return partial_bytes_r<12>(W, H, D, batch);
-        case 13: return partial_bytes_r<13>(W, H, D, batch);
-        case 14: return partial_bytes_r<14>(W, H, D, batch);
-        case 15: return partial_bytes_r<15>(W, H, D, batch);
-        default: return 0;
-    }
-}
-
-static hipError_t launch_box_right(const MatchArgs& a, int batch, const RightOut* rop, hipStream_t s) {
-    const RightOut& ro = *rop;
-    switch (a.radius) {
-        case 0: return launch_r<0, true>(a, batch, &ro, s);
-        case 1: return launch_r<1, true>(a, batch, &ro, s);
-        case 2: return launch_r<2, true>(a, batch, &ro, s);
-        case 3: return launch_r<3, true>(a, batch, &ro, s);
-        case 4: return launch_r<4, true>(a, batch, &ro, s);
-        case 5: return launch_r<5, true>(a, batch, &ro, s);
-        case 6: return launch_r<6, true>(a, batch, &ro, s);
-        case 7: return launch_r<7, true>(a, batch, &ro, s);
-        case 8: return launch_r<8, true>(a, batch, &ro, s);
-        case 9: return launch_r<9, true>(a, batch, &ro, s);
-        case 10: return launch_r<10, true>(a, batch, &ro, s);
-        case 11: return launch_r<11, true>(a, batch, &ro, s);
-        case 12: return launch_r<12, true>(a, batch, &ro, s);
-        case 13: return launch_r<13, true>(a, batch, &ro, s);
-        case 14: return launch_r<14, true>(a, batch, &ro, s);
-        case 15: return launch_r<15, true>(a, batch, &ro, s);
-        default: return hipErrorInvalidValue;
-    }
+static hipError_t launch_box_right(const MatchArgs& a, int batch, const RightOut& ro, hipStream_t s) {
+    return with_radius<0, kMaxBoxRadius>(a.radius, hipErrorInvalidValue, [&](auto r) {
+        return launch_r<decltype(r)::value, true>(a, batch, &ro, s);
+    });
 }
 
 hipError_t launch_box_match_lr(const MatchArgs& a, int batch, int check, uint8_t* right_out, uint8_t* mask_out,
                                int aux_pitch, int64_t aux_stride, hipStream_t s) {
     if (a.d_lo != 0 || a.valid_mode != 0 || !a.disp || !a.rpart || (!check && !right_out)) return hipErrorInvalidValue;
     const RightOut ro{check, right_out, mask_out, aux_pitch, aux_stride, nullptr};
-    return launch_box_right(a, batch, &ro, s);
+    return launch_box_right(a, batch, ro, s);
 }
 
 hipError_t launch_box_slice_lr_keys(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s) {
@@ -857,7 +753,7 @@ hipError_t launch_box_slice_lr_keys(const MatchArgs& a, int batch, uint32_t* rig
         a.d_hi > kMaxDisp)
         return hipErrorInvalidValue;
     const RightOut ro{0, nullptr, nullptr, 0, 0, right_keys};
-    return launch_box_right(a, batch, &ro, s);
+    return launch_box_right(a, batch, ro, s);
 }
 
 hipError_t launch_box_match_generic(const MatchArgs& a, int batch, hipStream_t s) {

@@ -700,13 +700,11 @@ hipError_t resident_workgroups(int* out) {
     const bool cached = dev >= 0 && dev < kMaxDevices;
     int v = cached ? slots[dev].load(std::memory_order_relaxed) : 0;
     if (v == 0) {
-        int per_cu = 0, cus = 0;
+        int per_cu = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, box_mfma_kernel<R, DMAX, NP>, kThreads,
                                                          (size_t)MG<R, DMAX, NP>::LDS_BYTES);
         if (e != hipSuccess) return e;
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        v = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+        v = (per_cu > 0 ? per_cu : 1) * device_cus();
         if (cached) slots[dev].store(v, std::memory_order_relaxed);
     }
     *out = v;
@@ -773,16 +771,8 @@ bool box_mfma_scope(const MatchArgs& a) {
 
 hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
     if (!box_mfma_scope(a)) return hipErrorInvalidValue;
-    switch (a.radius) {
-        case 1: return launch_r<1>(a, batch, s, workgroups);
-        case 2: return launch_r<2>(a, batch, s, workgroups);
-        case 3: return launch_r<3>(a, batch, s, workgroups);
-        case 4: return launch_r<4>(a, batch, s, workgroups);
-        case 5: return launch_r<5>(a, batch, s, workgroups);
-        case 6: return launch_r<6>(a, batch, s, workgroups);
-        case 7: return launch_r<7>(a, batch, s, workgroups);
-        default: return hipErrorInvalidValue;
-    }
+    return with_radius<1, kMaxFastRadius>(a.radius, hipErrorInvalidValue,
+                                          [&](auto r) { return launch_r<decltype(r)::value>(a, batch, s, workgroups); });
 }
 
 }  // namespace sm

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <type_traits>
+
 namespace sm {
 
 // Launch parameters of one block-matching pass over a batch of frames.
@@ -20,8 +23,36 @@ struct MatchArgs {
     int out_pitch;
     int64_t out_frame_stride;
     uint32_t* keys;         // optional: packed keys [batch][H][W] (multi-GPU slice reduction)
-    uint32_t* rpart;        // fused right view: per-tile right-key partials (box_right_partial_bytes)
+    uint32_t* rpart;        // fused right view: per-tile right-key partials (box_right_partial_bytes, bm_box_plan.h)
 };
+
+// The CU count of the current device, asked once per device index: the handles of a group on several devices size
+// each launch by their own device (256 when the query fails).
+inline int device_cus() {
+    constexpr int kMaxDevices = 64;
+    static std::atomic<int> count[kMaxDevices];   // 0: not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    const bool cached = dev >= 0 && dev < kMaxDevices;
+    int cus = cached ? count[dev].load(std::memory_order_relaxed) : 0;
+    if (cus == 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        if (cached) count[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
+// f(std::integral_constant<int, R>{}) for the R in [LO, HI] that equals r (the radius as a kernel's template
+// argument), else `fallback`
+template <int LO, int HI, class T, class F>
+T with_radius(int r, T fallback, F&& f) {
+    if constexpr (LO > HI) {
+        return fallback;
+    } else {
+        if (r == LO) return f(std::integral_constant<int, LO>{});
+        return with_radius<LO + 1, HI>(r, fallback, f);
+    }
+}
 
 constexpr int kMaxDisp = 256;      // uint8 output / 8-bit d field of the packed key
 constexpr int kNumXcd = 8;         // MI355X: 8 XCDs, each with its own L2
@@ -35,11 +66,10 @@ __device__ __forceinline__ int xcd_tile(int b, int nb) {
     return x < rem ? x * (per + 1) + i : rem * (per + 1) + (x - rem) * per + i;
 }
 constexpr int kMaxFastRadius = 7;  // u16 packed sums stay < 2^16 up to r = 7 (15*15*255 = 57375)
-// fused box matcher (bm_box.hip): u16 packed column prefixes stay < 2^16 up to r = 15
-// ((32 + 30) * 255 = 15810); r 8..15 sum the window's two halves in u32
-constexpr int kMaxBoxRadius = 15;
 
-// Host-side launchers (bm_box.hip, bm_aux.hip).
+// Host-side launchers (bm_box.hip, bm_aux.hip).  Which box launcher a pass takes, and the workspace sizes named
+// below, are bm_box_plan.h's (plan_box_pass); a launcher checks only its own arguments.
+// The fused tile kernels, radius <= kMaxBoxRadius (hipErrorInvalidValue beyond).
 // box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the VALU kernels of bm_box.hip, 2 the matrix-pipe kernel
 // (bm_box_mfma.hip) wherever box_mfma_scope holds
 // box_workgroups (SM_PARAM_BOX_WORKGROUPS): workgroups of a matrix-pipe launch, each walking a contiguous range of
@@ -49,18 +79,18 @@ hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int bo
 // view; bit-exact with launch_box_match.  hipErrorInvalidValue outside box_mfma_scope
 bool box_mfma_scope(const MatchArgs& a);
 hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups = 0);
+// any radius: the direct window sum per (pixel, d), straight from the reference formulation; not a performance path
 hipError_t launch_box_match_generic(const MatchArgs& a, int batch, hipStream_t s);
 // Box matching + right view (+ LR check) in two launches (radius <= kMaxBoxRadius, d_lo == 0).
 // check = 1: a.disp receives the checked left disparity, right_out/mask_out (optional) dR and the
 // valid mask.  check = 0: a.disp the unchecked left map and right_out (required) dR.
 hipError_t launch_box_match_lr(const MatchArgs& a, int batch, int check, uint8_t* right_out, uint8_t* mask_out,
                                int aux_pitch, int64_t aux_stride, hipStream_t s);
-size_t box_right_partial_bytes(int W, int H, int radius, int D, int batch);
 // d-slice with LR (multi-GPU): one fused pass over d in [a.d_lo, a.d_hi) (radius <= kMaxBoxRadius)
 // writing the left slice keys to a.keys (as launch_box_match) and the right view's slice keys
 // min over d in the slice with u + d < W of (C_L(u + d, d) << 8 | d) to right_keys [batch][H][W]
 // (0x7FFFFFFF where none; every key < 2^31 at these radii): keys of disjoint slices combine with a MIN.  a.rpart:
-// box_right_partial_bytes(W, H, radius, d_hi - d_lo, batch) bytes.
+// the plan's rpart_bytes (bm_box_plan.h).
 hipError_t launch_box_slice_lr_keys(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s);
 // acc = min(acc, src) elementwise over n unsigned keys
 hipError_t launch_min_keys_u32(uint32_t* acc, const uint32_t* src, int64_t n, hipStream_t s);
@@ -93,8 +123,8 @@ hipError_t launch_all_sad_generic(const uint8_t* L, const uint8_t* R, int W, int
 hipError_t launch_volume_wta(const uint16_t* sad, int W, int H, int D, int frames, uint32_t seed_key, uint8_t* disp,
                              int out_pitch, int64_t out_stride, hipStream_t s);
 // radius 16..127 (bm_wide.hip): V planes (u16, (d_hi - d_lo) * W * H per frame of a launch group, in `ws`,
-// wide_workspace_bytes) then one block per image row; a.valid_mode 0, 4 <= W <= 4096.  right (optional): the right view's dR [batch][H][rpitch]
-size_t wide_workspace_bytes(int W, int H, int D, int batch);
+// wide_workspace_bytes) then one block per image row; a.valid_mode 0, wide_frame(W, H, pitch).  right (optional): the
+// right view's dR [batch][H][rpitch]
 // rkeys (d-slices with LR): the right view's raw keys [batch][H][W] of the slice [a.d_lo, a.d_hi), sign bit flipped
 // (kRightKeyFlip), instead of / beside `right`
 hipError_t launch_box_match_wide(const MatchArgs& a, int batch, uint16_t* ws, uint8_t* right, int rpitch,
@@ -103,28 +133,13 @@ hipError_t launch_box_match_wide(const MatchArgs& a, int batch, uint16_t* ws, ui
 // like the unsigned keys at every radius (a wide window's key reaches 255 * 255^2 << 8 > 2^31 from r = 91), and
 // "no d of the slice reaches u" (0xFFFFFFFF before the flip) is INT32_MAX, as for the guided keys.
 constexpr uint32_t kRightKeyFlip = 0x80000000u;
-// radius 16..37 without the right view (bm_strip.hip; valid_mode 0 or 1, the mirrored right-view pass of frames
-// wider than the separable path takes): disparities across the lanes, vertical sums in registers,
-// no workspace; strip_path says whether a pass takes it (SM_WIDE_STRIP=0, read once, turns it off for A/B).  Past
-// r = 37 the strip's 128 - 2r outputs per 128 summed columns make it slower than the separable path (1080p D=128,
-// us per frame: r = 37 223.4 vs 236.3, r = 40 256.6 vs 236.6)
-constexpr int kStripMinRadius = 16;
-#ifndef SM_STRIP_MAX_R
-#define SM_STRIP_MAX_R 37
-#endif
-constexpr int kStripMaxRadius = SM_STRIP_MAX_R;
-bool strip_path(const MatchArgs& a);
+// radius 16..37 (bm_strip.hip; valid_mode 0 or 1, the mirrored right-view pass of frames the separable path
+// rejects): disparities across the lanes, vertical sums in registers, no workspace
 hipError_t launch_box_match_strip(const MatchArgs& a, int batch, hipStream_t s);
 // the same with the right view (a.valid_mode 0, a.d_lo 0; bm_strip_lr.hip): right_keys [batch][H][W], filled with
 // ~0 by the caller, receives the MIN over d of (C_L(u + d, d) << 8 | d) over d <= u + d < W: the separable path's
 // right-view keys, whose low byte is dR
 hipError_t launch_box_match_strip_lr(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s);
-constexpr int kMaxWideWidth = 4096;
-// radius 16..127, 4 <= W <= 4096 and frames below 2^31 bytes (its buffer loads address a frame with 32-bit
-// offsets) take the separable wide-window path (bm_wide.hip); the rest the generic kernel
-inline bool wide_path(int radius, int W, int H, int pitch) {
-    return radius > kMaxBoxRadius && W >= 4 && W <= kMaxWideWidth && (int64_t)pitch * H < ((int64_t)1 << 31);
-}
 // SM_DEVICE_CU_GRID (bm_literal.hip): Device.cu's literal map, AD only for rows < 256 and cols < 320, all zero
 // for W > 1024; needs W >= 320, H >= 256 and literal_workspace_bytes(D) of device scratch in `ws`
 size_t literal_workspace_bytes(int D);

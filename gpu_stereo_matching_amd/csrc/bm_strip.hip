@@ -22,9 +22,9 @@
 // 1080p, D = 128, 8 frames per call (us per frame, MI355X, same box, against the separable path's 234-237):
 // r = 16 141.9, r = 20 150.7, r = 25 180.2, r = 31 203.9, r = 37 223.4.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
+#include "bm_box_plan.h"
 #include "bm_common.h"
 
 namespace sm {
@@ -34,24 +34,9 @@ constexpr int kSC = 128;      // input columns per strip
 constexpr int kSP = kSC / 2;  // u16 column pairs per strip row
 constexpr int kSQ = kSC / 4;  // 4-column groups per strip
 constexpr int kNT = 256;      // max threads per workgroup (4 waves: d spans up to 256)
-#ifndef SM_STRIP_WPE
-#define SM_STRIP_WPE 4        // waves per SIMD the register budget is sized for
-#endif
-#ifndef SM_STRIP_LA
-#define SM_STRIP_LA 1         // 4-column groups whose LDS reads are in flight ahead of the one being summed
-#endif
-#ifndef SM_STRIP_ADOR
-#define SM_STRIP_ADOR 1       // |a - b| as (a -sat b) | (b -sat a) (2 % faster than max - min at r = 20)
-#endif
-#ifndef SM_STRIP_CH2
-#define SM_STRIP_CH2 0        // 1: the row's window sums as two independent chains (first / second half of the groups)
-#endif
-#ifndef SM_STRIP_VMASK
-#define SM_STRIP_VMASK 1
-#endif
-#ifndef SM_STRIP_ONELOOP
-#define SM_STRIP_ONELOOP 0
-#endif
+constexpr int kWPE = 4;       // waves per SIMD the register budget is sized for
+constexpr int kLA = 1;        // 4-column groups whose LDS reads are in flight ahead of the one being summed
+static_assert(kNT == kStripMaxDisp, "one lane per disparity of a pass the plan sends here (bm_box_plan.h)");
 // every lambda of the kernel inlined: one left out of line takes V (captured by reference) to scratch
 #define SM_INL __attribute__((always_inline))
 
@@ -89,7 +74,7 @@ constexpr int stage_bytes(int RS) { return 2 * kSP * 4 + 2 * 2 * RS * 4; }
 // u = x - d >= 0, StereoHelper.cpp:156-180, as the separable path's hwta kernel) and flushed into rk, the frame's
 // right keys [batch][H][W] (filled with ~0 by the caller), by global atomic min (strips overlap in u)
 template <int R, bool RIGHT>
-__global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t* __restrict__ Limg, const uint8_t* __restrict__ Rimg,
+__global__ __launch_bounds__(kNT, kWPE) void strip_kernel(const uint8_t* __restrict__ Limg, const uint8_t* __restrict__ Rimg,
                                                     int64_t fstride, int W, int H, int pitch, int d_lo, int d_hi, int EL,
                                                     int NI, int nb, int nbe, int vm,
                                                     int DP, int RW, int RS, int nw, uint32_t seed, uint32_t thresh,
@@ -212,14 +197,13 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
     for (int p = 0; p < kSP; ++p) V[p] = 0u;
 
     // one step's rows: AD of the in row into V and (OUT) of the out row out of it, from buffer buf.  The LDS reads of
-    // 4-column group q + SM_STRIP_LA are issued before group q's arithmetic
+    // 4-column group q + kLA are issued before group q's arithmetic
     auto update = [&](int buf, auto edge, auto with_out) SM_INL {
         constexpr bool EDGE = decltype(edge)::value;
         constexpr bool OUT = decltype(with_out)::value;
         const uint8_t* B = lds + buf * BUF;
         const uint2* Ls = reinterpret_cast<const uint2*>(B);       // [2][kSQ]
         const uint32_t* Rr = reinterpret_cast<const uint32_t*>(B + 2 * kSP * 4) + rword;   // row io at + io * 2 * RS
-#if SM_STRIP_VMASK
         // edge strips: the AD is summed unmasked and V is cleared afterwards at the columns outside [clo, chi) (what
         // they hold is never read before the next clear): 4 VALU per register and step instead of a select per
         // column and row.  mw[i]: bit c of the 32 columns 32 i .. 32 i + 31 set where the column counts
@@ -236,13 +220,6 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
                 mw[i] = lo & hi;
             }
         }
-        int mlo = 0, mhi = 0;
-#else
-        // opaque copies of the mask bounds: otherwise the column compares, loop-invariant, are hoisted out of the
-        // row loop into 128 SGPR pairs and spilled
-        int mlo = clo, mhi = chi;
-        if constexpr (EDGE) asm volatile("" : "+v"(mlo), "+v"(mhi));
-#endif
         struct G { uint2 li, lo; uint32_t ri0, ri1, ro0, ro1; };
         auto load = [&](int q) SM_INL {
             G g;
@@ -256,36 +233,27 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
             }
             return g;
         };
-        auto ad = [&](uint32_t l, uint32_t r, int c) SM_INL {
+        // |a - b| = (a -sat b) | (b -sat a): two packed clamped subtracts and a VOP2 or (2 % faster than max - min
+        // at r = 20)
+        auto ad = [&](uint32_t l, uint32_t r) SM_INL {
             const u16x2 a = as16(l), b = as16(r);
-#if SM_STRIP_ADOR
-            // |a - b| = (a -sat b) | (b -sat a): two packed clamped subtracts and a VOP2 or
-            u16x2 e = as16(as32(__builtin_elementwise_sub_sat(a, b)) | as32(__builtin_elementwise_sub_sat(b, a)));
-#else
-            u16x2 e = __builtin_elementwise_max(a, b) - __builtin_elementwise_min(a, b);
-#endif
-            if constexpr (EDGE && !SM_STRIP_VMASK) {
-                e.x = (c >= mlo && c < mhi) ? e.x : (unsigned short)0;
-                e.y = (c + 1 >= mlo && c + 1 < mhi) ? e.y : (unsigned short)0;
-            }
-            return e;
+            return as16(as32(__builtin_elementwise_sub_sat(a, b)) | as32(__builtin_elementwise_sub_sat(b, a)));
         };
         G g[kSQ];
 #pragma unroll
-        for (int q = 0; q < SM_STRIP_LA && q < kSQ; ++q) g[q] = load(q);
+        for (int q = 0; q < kLA && q < kSQ; ++q) g[q] = load(q);
 #pragma unroll
         for (int q = 0; q < kSQ; ++q) {
-            if (q + SM_STRIP_LA < kSQ) g[q + SM_STRIP_LA] = load(q + SM_STRIP_LA);
+            if (q + kLA < kSQ) g[q + kLA] = load(q + kLA);
             const G& cur = g[q];
-            u16x2 v0 = as16(V[2 * q]) + ad(cur.li.x, cur.ri0, 4 * q);
-            u16x2 v1 = as16(V[2 * q + 1]) + ad(cur.li.y, cur.ri1, 4 * q + 2);
+            u16x2 v0 = as16(V[2 * q]) + ad(cur.li.x, cur.ri0);
+            u16x2 v1 = as16(V[2 * q + 1]) + ad(cur.li.y, cur.ri1);
             if constexpr (OUT) {
-                v0 = v0 - ad(cur.lo.x, cur.ro0, 4 * q);
-                v1 = v1 - ad(cur.lo.y, cur.ro1, 4 * q + 2);
+                v0 = v0 - ad(cur.lo.x, cur.ro0);
+                v1 = v1 - ad(cur.lo.y, cur.ro1);
             }
             V[2 * q] = as32(v0);
             V[2 * q + 1] = as32(v1);
-#if SM_STRIP_VMASK
             if constexpr (EDGE) {
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -297,7 +265,6 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
                     V[2 * q + k] &= (m0 & 0xFFFFu) | (m1 & 0xFFFF0000u);
                 }
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -392,19 +359,9 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
             for (int c = 8 * g0; c < 8 * g0 + 2 * R; ++c) S = sacc(S, c, std::true_type{});
             return S;
         };
-        if constexpr (SM_STRIP_CH2 != 0 && NG >= 2) {
-            constexpr int NGA = (NG + 1) / 2;
-            uint32_t SA = init(0), SB = init(NGA);
+        uint32_t S = init(0);
 #pragma unroll
-            for (int i = 0; i < NGA; ++i) {
-                SA = grp(SA, i);
-                if (NGA + i < NG) SB = grp(SB, NGA + i);
-            }
-        } else {
-            uint32_t S = init(0);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) S = grp(S, g);
-        }
+        for (int g = 0; g < NG; ++g) S = grp(S, g);
         if ((lane & 7) == 0) {
             uint32_t* wm = wmin + (wb * nw + wave) * (NG * 8) + (lane >> 3);
 #pragma unroll
@@ -436,9 +393,6 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
     // y0 + s - 2R is complete
     const int nsteps = 2 * R + (y1 - y0);
     if (nsteps <= 2 * R) return;
-#ifndef SM_STRIP_SKIP
-#define SM_STRIP_SKIP 0   // timing only (wrong maps): 1 no staging, 2 no V update, 4 no row WTA
-#endif
     // step s reads rows y0 - R + s (in) and y0 - 3R - 1 + s (out; staged as zeros before step 2R + 1, where nothing
     // leaves V: the steps from 2R on then run one uniform body)
     auto rows_of = [&](int st, int& yin, int& yout) SM_INL {
@@ -468,7 +422,7 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
         const int buf = st & 1;
         [[maybe_unused]] uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
         SM_STAMP(t0);
-        if (!(SM_STRIP_SKIP & 1) && st + 1 < nsteps) {
+        if (st + 1 < nsteps) {
             store(buf ^ 1);
             if (st + 2 < nsteps) {
                 int a, b;
@@ -477,15 +431,13 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
             }
         }
         SM_STAMP(t1);
-        if (!(SM_STRIP_SKIP & 2)) update(buf, edge, with_out);
+        update(buf, edge, with_out);
         SM_STAMP(t2);
-        if (decltype(with_out)::value && (SM_STRIP_ONELOOP == 0 || st >= 2 * R)) {
-            if (!(SM_STRIP_SKIP & 4)) {
-                const int wb = (st - 2 * R) & 1;
-                row_wta(wb, edge);                                // the masked keys go with the masked columns
-                SM_STAMP(t3);
-                if (st > 2 * R) emit(wb ^ 1, y0 + st - 2 * R - 1);   // written in the step before, behind its barrier
-            }
+        if (decltype(with_out)::value) {
+            const int wb = (st - 2 * R) & 1;
+            row_wta(wb, edge);                                // the masked keys go with the masked columns
+            SM_STAMP(t3);
+            if (st > 2 * R) emit(wb ^ 1, y0 + st - 2 * R - 1);   // written in the step before, behind its barrier
         }
         SM_STAMP(t4);
         if constexpr (RIGHT) asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");   // the inline ds_min_u32s
@@ -502,13 +454,12 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
         }
 #endif
     };
-    // the edge strips (columns outside the frame or below d, outputs past W or with invalid d) take the masked body
-    // SM_STRIP_ONELOOP: one loop body for every step (the first 2R subtract staged zero rows: a third less code, but
-    // 8 % slower at r = 20), else a separate add-only loop for them
+    // the edge strips (columns outside the frame or below d, outputs past W or with invalid d) take the masked body;
+    // the first 2R steps, which only build V, an add-only loop of their own (one loop body subtracting staged zero
+    // rows: a third less code, but 8 % slower at r = 20)
     auto run = [&](auto edge) SM_INL {
         int st = 0;
-        if constexpr (SM_STRIP_ONELOOP == 0)
-            for (; st < 2 * R; ++st) step(st, edge, std::false_type{});
+        for (; st < 2 * R; ++st) step(st, edge, std::false_type{});
         for (; st < nsteps; ++st) step(st, edge, std::true_type{});
     };
     if (col_ok && out_ok) run(std::false_type{});
@@ -523,35 +474,14 @@ __global__ __launch_bounds__(kNT, SM_STRIP_WPE) void strip_kernel(const uint8_t*
         for (int i = 0; i < 5; ++i) __builtin_memcpy(disp + 8 * i, &prof[i], 8);
     }
 #endif
-    if constexpr ((SM_STRIP_SKIP & 4) != 0) {   // keep the V update live in the timing-only build
-        uint32_t t = 0;
-#pragma unroll
-        for (int p = 0; p < kSP; ++p) t ^= V[p];
-        if (t == 0x12345u && keys) keys[0] = t;
-    }
-}
-
-int device_cus() {
-    static const int n = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        return cus;
-    }();
-    return n;
 }
 
 // Row bands, one round of workgroups (a second, partial round would leave most of the chip idle while it runs):
 // interior strips in nb bands, edge strips in nbe, chosen to minimise the longer of the two band walks, a band of
-// height h costing (h + 2r) row steps (its first 2r steps only build V), an edge step SM_STRIP_EDGE_COST % of an
+// height h costing (h + 2r) row steps (its first 2r steps only build V), an edge step kEdgeCost % of an
 // interior one (the masked body), over the (nb, nbe) whose workgroups all fit at once.
-#ifndef SM_STRIP_EDGE_COST
-#define SM_STRIP_EDGE_COST 150
-#endif
-#ifndef SM_STRIP_FILL
-#define SM_STRIP_FILL 100   // percent of the resident workgroups the bands aim at
-#endif
+constexpr int kEdgeCost = 150;
+constexpr int kFill = 100;   // percent of the resident workgroups the bands aim at
 struct StripGrid {
     int EL, NI, ER;   // left edge, interior and right edge strips
     int nb, nbe;      // bands per interior / edge strip
@@ -578,7 +508,7 @@ StripGrid strip_grid(const MatchArgs& a, int R, int SW, int frames, int resident
             const int64_t blocks = ((int64_t)ne * nbe + (int64_t)g.NI * nb) * frames;
             if (blocks > resident && !(nb == 1 && nbe == 1)) continue;
             const int64_t ti = g.NI ? (int64_t)((a.H + nb - 1) / nb + 2 * R) * 100 : 0;
-            const int64_t te = ne ? (int64_t)((a.H + nbe - 1) / nbe + 2 * R) * SM_STRIP_EDGE_COST : 0;
+            const int64_t te = ne ? (int64_t)((a.H + nbe - 1) / nbe + 2 * R) * kEdgeCost : 0;
             const int64_t t = std::max(ti, te);
             if (best < 0 || t < best) {
                 best = t;
@@ -602,7 +532,7 @@ hipError_t launch_strip_r(const MatchArgs& a, int batch, hipStream_t s, uint32_t
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, strip_kernel<R, RIGHT>, 64 * nw, lds) != hipSuccess ||
         per_cu <= 0)
         per_cu = 1;
-    const StripGrid g = strip_grid(a, R, SW, batch, per_cu * device_cus() * SM_STRIP_FILL / 100);
+    const StripGrid g = strip_grid(a, R, SW, batch, per_cu * device_cus() * kFill / 100);
     const int64_t nblk = (int64_t)(g.EL + g.ER) * g.nbe + (int64_t)g.NI * g.nb;
     if (nblk > 0x7FFFFFFF || batch > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL((strip_kernel<R, RIGHT>), dim3((unsigned)nblk, 1u, (unsigned)batch), dim3(64 * nw), lds, s,
@@ -612,40 +542,31 @@ hipError_t launch_strip_r(const MatchArgs& a, int batch, hipStream_t s, uint32_t
     return hipGetLastError();
 }
 
-template <int R, bool RIGHT>
+// what the kernel takes: the plan's strip_path (bm_box_plan.h) and a known valid_mode
+bool strip_args_ok(const MatchArgs& a, int batch) {
+    return strip_path(BoxGeom{a.W, a.H, a.pitch, a.radius, a.d_lo, a.d_hi, batch}) && batch > 0 &&
+           (a.valid_mode == 0 || a.valid_mode == 1);
+}
+
+template <bool RIGHT>
 hipError_t dispatch_strip(const MatchArgs& a, int batch, hipStream_t s, uint32_t* rk) {
-    if constexpr (R > kStripMaxRadius) {
-        return hipErrorInvalidValue;
-    } else {
-        if (a.radius == R) return launch_strip_r<R, RIGHT>(a, batch, s, rk);
-        return dispatch_strip<R + 1, RIGHT>(a, batch, s, rk);
-    }
+    return with_radius<kStripMinRadius, kStripMaxRadius>(a.radius, hipErrorInvalidValue, [&](auto r) {
+        return launch_strip_r<decltype(r)::value, RIGHT>(a, batch, s, rk);
+    });
 }
 
 }  // namespace
 
 #ifndef SM_STRIP_RIGHT_TU
-bool strip_path(const MatchArgs& a) {
-    static const bool on = [] {
-#ifdef SM_STRIP_OFF
-        return false;   // A/B builds
-#endif
-        const char* e = getenv("SM_WIDE_STRIP");
-        return !(e && e[0] == '0');
-    }();
-    return on && a.radius >= kStripMinRadius && a.radius <= kStripMaxRadius && (a.valid_mode == 0 || a.valid_mode == 1) &&
-           a.d_hi > a.d_lo && a.d_hi <= kMaxDisp && a.W >= 4 && a.H >= 1;
-}
-
 hipError_t launch_box_match_strip(const MatchArgs& a, int batch, hipStream_t s) {
-    if (!strip_path(a) || batch <= 0) return hipErrorInvalidValue;
-    return dispatch_strip<kStripMinRadius, false>(a, batch, s, nullptr);
+    if (!strip_args_ok(a, batch)) return hipErrorInvalidValue;
+    return dispatch_strip<false>(a, batch, s, nullptr);
 }
 #else
 // bm_strip_lr.hip: the instantiations with the right view, compiled in their own translation unit
 hipError_t launch_box_match_strip_lr(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s) {
-    if (!strip_path(a) || a.valid_mode != 0 || a.d_lo != 0 || !right_keys || batch <= 0) return hipErrorInvalidValue;
-    return dispatch_strip<kStripMinRadius, true>(a, batch, s, right_keys);
+    if (!strip_args_ok(a, batch) || a.valid_mode != 0 || a.d_lo != 0 || !right_keys) return hipErrorInvalidValue;
+    return dispatch_strip<true>(a, batch, s, right_keys);
 }
 #endif
 

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "bm_box_plan.h"
 #include "bm_common.h"
 
 namespace sm {
@@ -343,29 +344,14 @@ hipError_t launch_span(const uint16_t* V, int W, int H, int radius, int d_lo, in
     return launch_h<NPT, 256>(V, W, H, radius, d_lo, d_hi, seed, thresh, out, frames, s);
 }
 
-// frames per vsum / hwta launch pair: enough row blocks for ~32 per CU (1080 rows of one 1080p frame give 4),
-// at most 8 frames and 4.5 GB of V planes (1080p D=128: 8 frames, 4.2 GB).  Same box, 1080p D=128, 8 frames per
-// call (profiles/microbench/r05_wide_path.txt): 2 / 4 / 8 frames per pair 0.280 / 0.268 / 0.265 ms at r = 16,
-// 0.280 / 0.251 / 0.239 at r = 127
-int wide_group(int W, int H, int D, int batch) {
-    const int64_t plane = (int64_t)W * H * D * (int64_t)sizeof(uint16_t);
-    const int by_mem = (int)std::max<int64_t>(1, ((int64_t)4608 << 20) / std::max<int64_t>(plane, 1));
-    const int want = (8192 + H - 1) / H;
-    return std::max(1, std::min({want, batch, 8, by_mem}));
-}
-
 }  // namespace
-
-size_t wide_workspace_bytes(int W, int H, int D, int batch) {
-    return (size_t)wide_group(W, H, D, batch) * D * W * H * sizeof(uint16_t);
-}
 
 hipError_t launch_box_match_wide(const MatchArgs& a, int batch, uint16_t* ws, uint8_t* right, int rpitch,
                                  int64_t rstride, hipStream_t s, uint32_t* rkeys) {
-    if (!wide_path(kMaxBoxRadius + 1, a.W, a.H, a.pitch) || a.valid_mode != 0 || a.d_hi <= a.d_lo || batch <= 0)
+    if (!wide_frame(a.W, a.H, a.pitch) || a.valid_mode != 0 || a.d_hi <= a.d_lo || batch <= 0)
         return hipErrorInvalidValue;
     const int nd = a.d_hi - a.d_lo;
-    const int G = wide_group(a.W, a.H, nd, batch);
+    const int G = wide_group(a.W, a.H, nd, batch);   // frames per launch pair: ws holds their V planes (bm_box_plan.h)
     // row chunks: enough waves to fill the chip (~32 per CU), each chunk at least a window tall (its prologue
     // re-reads the 2r + 1 rows above it, from L2)
     const unsigned gx = (unsigned)((a.W + 4 * kVT - 1) / (4 * kVT));
@@ -398,8 +384,8 @@ hipError_t launch_box_match_wide(const MatchArgs& a, int batch, uint16_t* ws, ui
             e = launch_span<1024>(ws, a.W, a.H, a.radius, a.d_lo, a.d_hi, a.seed_key, a.thresh_key, out, n, s);
         else if (a.W <= 2048)
             e = launch_span<2048>(ws, a.W, a.H, a.radius, a.d_lo, a.d_hi, a.seed_key, a.thresh_key, out, n, s);
-        else
-            e = launch_span<4096>(ws, a.W, a.H, a.radius, a.d_lo, a.d_hi, a.seed_key, a.thresh_key, out, n, s);
+        else   // wide_frame: W <= kMaxWideWidth
+            e = launch_span<kMaxWideWidth>(ws, a.W, a.H, a.radius, a.d_lo, a.d_hi, a.seed_key, a.thresh_key, out, n, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -90,6 +90,75 @@ int upload_pair(sm_handle* h, const uint8_t* left, const uint8_t* right, int W, 
     return SM_OK;
 }
 
+int run_box_pass(WsScope& ws, sm_handle* h, sm::MatchArgs a, int batch, const sm::BoxPlan& p, const BoxRightOut& r) {
+    using sm::BoxLeft;
+    using sm::BoxRight;
+    hipStream_t s = ws.stream();
+    const int64_t P = (int64_t)a.W * a.H, PB = P * batch;
+    if (p.right == BoxRight::Unsupported)
+        return fail(SM_ERR_INVALID_ARG, "box radius %d: no right-view keys outside the wide path", a.radius);
+    uint8_t* vol = nullptr;
+    if (p.rpart_bytes) {
+        int rc = ws.get(h->rpart, p.rpart_bytes, &a.rpart);
+        if (rc) return rc;
+    }
+    if (p.vol_bytes) {
+        int rc = ws.get(h->vol, p.vol_bytes, &vol);
+        if (rc) return rc;
+    }
+    const bool fused = p.right == BoxRight::Fused;
+    switch (p.left) {
+        case BoxLeft::Tile:
+            if (!fused)
+                SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel, h->box_workgroups));
+            else if (r.keys)
+                SM_HIP(sm::launch_box_slice_lr_keys(a, batch, r.keys, s));
+            else
+                SM_HIP(sm::launch_box_match_lr(a, batch, r.check, r.map, r.mask, r.pitch, r.stride, s));
+            break;
+        case BoxLeft::Strip:
+            if (!fused) {
+                SM_HIP(sm::launch_box_match_strip(a, batch, s));
+            } else {   // the right keys through the volume workspace; their low byte is dR
+                uint32_t* rk = reinterpret_cast<uint32_t*>(vol);
+                SM_HIP(hipMemsetAsync(rk, 0xFF, (size_t)PB * 4, s));
+                SM_HIP(sm::launch_box_match_strip_lr(a, batch, rk, s));
+                SM_HIP(sm::launch_keys_low_byte(rk, PB, r.map, s));
+            }
+            break;
+        case BoxLeft::Wide:
+            SM_HIP(sm::launch_box_match_wide(a, batch, reinterpret_cast<uint16_t*>(vol), r.map, r.pitch, r.stride, s,
+                                             r.keys));
+            break;
+        case BoxLeft::Direct:
+            SM_HIP(sm::launch_box_match_generic(a, batch, s));
+            break;
+    }
+    if (p.right != BoxRight::Mirrored) return SM_OK;
+    // the right map on the mirrored pair (StereoHelper.cpp:156-180 + :131-154): valid d <= x, no threshold; the
+    // map stays mirrored
+    uint8_t* mL = r.mirror;
+    uint8_t* mR = mL + PB;
+    SM_HIP(sm::launch_mirror(a.right, a.W, a.H, a.pitch, a.frame_stride, batch, mL, a.W, P, s));
+    SM_HIP(sm::launch_mirror(a.left, a.W, a.H, a.pitch, a.frame_stride, batch, mR, a.W, P, s));
+    sm::MatchArgs b = a;
+    b.left = mL;
+    b.right = mR;
+    b.pitch = a.W;
+    b.frame_stride = P;
+    b.valid_mode = 1;
+    b.seed_key = 0xFFFFFFFFu;
+    b.thresh_key = 0xFFFFFFFFu;
+    b.disp = r.map;
+    b.out_pitch = r.pitch;
+    b.out_frame_stride = r.stride;
+    if (p.left == BoxLeft::Strip)
+        SM_HIP(sm::launch_box_match_strip(b, batch, s));
+    else
+        SM_HIP(sm::launch_box_match_generic(b, batch, s));
+    return SM_OK;
+}
+
 }  // namespace smh
 
 using namespace smh;
@@ -144,22 +213,12 @@ int run_staged(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
     return SM_OK;
 }
 
-// SM_STRIP_LR=0 (read once) keeps box + LR at r 16..37 on the separable path (A/B)
-bool strip_lr_enabled() {
-#ifdef SM_STRIP_LR_OFF
-    return false;   // A/B builds
-#endif
-    static const bool on = env_switch("SM_STRIP_LR", true);
-    return on;
-}
-
 // Core device-side pass over `batch` frames.  Workspace planes (lr) are dense W x H frames.
 //   left map  : matched straight into `disp`, or into a workspace plane when SM_MEDIAN filters it
 //               into `disp` afterwards (StereoDisparity.cpp:85/119);
-//   right map : fused with the left pass for box r <= 15 and for guided (right keys from
-//               the left costs, bm_guided.hip); box r = 16..127 takes it from the wide kernel's LDS
-//               atomic-min row (bm_wide.hip); only frames the wide path rejects (W > 4096, or planes of
-//               2^31 bytes and up) match the mirrored pair (valid d <= x, no threshold), kept mirrored;
+//   right map : box as plan_box_pass says (bm_box_plan.h: fused with the left pass, or for the frames the wide
+//               path rejects from the mirrored pair, kept mirrored); guided fused with the left pass (right keys
+//               from the left costs, bm_guided.hip);
 //   LR check  : StereoDisparity.cpp:136-147 on the (median-filtered, :119-126) maps.
 // Every workspace comes through `ws`, which orders the pass after the handle's last one on another stream: a
 // branch that takes none (box r <= 15 or the strip kernel without median and LR, guided without LR) stays
@@ -185,11 +244,7 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         if (rc) return rc;
     }
     const bool volume = sgm || census;   // both maps come out of one cost volume (run_volume)
-    const bool fused_right = lr && !guided && !volume && radius <= sm::kMaxBoxRadius;
     const bool guided_right = lr && guided;   // right view fused into the guided pass (bm_guided.hip)
-    // box r > 15: the separable wide-window path (bm_wide.hip), right view included; wider frames keep the
-    // direct generic kernel and the mirrored LR pass
-    const bool wide = !guided && !volume && sm::wide_path(radius, W, H, pitch);
     if ((flags & SM_DEVICE_CU_GRID) != 0) {   // Device.cu's launch geometry, frame by frame (bm_literal.hip)
         if (flags != SM_DEVICE_CU_GRID || lr)
             return fail(SM_ERR_INVALID_ARG, "SM_DEVICE_CU_GRID is box aggregation only (flags 0x%x)", flags);
@@ -212,9 +267,13 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         return run_staged(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, med, disp, opitch, ostride);
     }
 
-    // workspace: [left raw (med)] [right (lr)] [right filtered (lr && med)] [mirrored L, R (lr, not fused)]
-    const bool mirrored = lr && !fused_right && !guided_right && !wide && !volume;
-    const int64_t n_planes = (med ? 1 : 0) + (lr ? 1 : 0) + (lr && med ? 1 : 0) + (mirrored ? 2 : 0);
+    const bool box = !guided && !volume;
+    sm::BoxPlan plan{};
+    if (box)
+        plan = sm::plan_box_pass({W, H, pitch, radius, 0, D, batch}, lr ? sm::RightWant::Map : sm::RightWant::None);
+    // workspace: [left raw (med)] [right (lr)] [right filtered (lr && med)] [mirrored L, R (the plan's)]
+    const bool mirrored = plan.right == sm::BoxRight::Mirrored;
+    const int64_t n_planes = (med ? 1 : 0) + (lr ? 1 : 0) + (lr && med ? 1 : 0) + plan.mirror_planes;
     uint8_t* planes = nullptr;
     if (n_planes > 0) {
         int rc = ws.get(h->lr, (size_t)(n_planes * PB), &planes);
@@ -226,8 +285,7 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
     if (lr) planes += PB;
     uint8_t* right_med = (lr && med) ? planes : nullptr;
     if (lr && med) planes += PB;
-    uint8_t* mL = mirrored ? planes : nullptr;
-    uint8_t* mR = mL ? mL + PB : nullptr;
+    uint8_t* mirror = mirrored ? planes : nullptr;
 
     // ---- left map ----
     uint8_t* lmap = med ? left_raw : disp;
@@ -251,14 +309,6 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         const VolumeOut o{lmap, lpitch, lstride, lr ? right_map : nullptr};
         int rc = run_volume(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, sgm, census, sgm_p1, sgm_p2, o);
         if (rc) return rc;
-    } else if (fused_right) {
-        int rc = ws.get(h->rpart, sm::box_right_partial_bytes(W, H, radius, D, batch), &a.rpart);
-        if (rc) return rc;
-        if (!med) {   // match + right view + check in one pass over the partials
-            SM_HIP(sm::launch_box_match_lr(a, batch, 1, right_out, mask_out, apitch, astride, s));
-            return SM_OK;
-        }
-        SM_HIP(sm::launch_box_match_lr(a, batch, 0, right_map, nullptr, W, P, s));
     } else if (guided_right) {
         int* rpart = nullptr;
         int rc = ws.get(h->rpart, sm::guided_right_partial_bytes(W, H, radius, D, batch), &rpart);
@@ -268,56 +318,28 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
     } else if (guided) {
         SM_HIP(sm::launch_guided_match(L, R, W, H, pitch, batch, fstride, radius, D, h->guided_eps, 0, lmap, lpitch,
                                       lstride, s));
-    } else if (wide) {
-        // r 16..37: the strip kernel (bm_strip.hip); without the right view it needs no workspace, with it the
-        // right keys go through the volume workspace (4 B per pixel) and their low byte is dR
-        if (!lr && sm::strip_path(a)) {
-            SM_HIP(sm::launch_box_match_strip(a, batch, s));
-        } else if (lr && strip_lr_enabled() && sm::strip_path(a)) {
-            uint32_t* rk = nullptr;
-            int rc = ws.get(h->vol, (size_t)PB * 4, &rk);
-            if (rc) return rc;
-            SM_HIP(hipMemsetAsync(rk, 0xFF, (size_t)PB * 4, s));
-            SM_HIP(sm::launch_box_match_strip_lr(a, batch, rk, s));
-            SM_HIP(sm::launch_keys_low_byte(rk, PB, right_map, s));
-        } else {
-            uint16_t* v = nullptr;
-            int rc = ws.get(h->vol, sm::wide_workspace_bytes(W, H, D, batch), &v);
-            if (rc) return rc;
-            SM_HIP(sm::launch_box_match_wide(a, batch, v, lr ? right_map : nullptr, W, P, s));
-        }
-    } else if (radius > sm::kMaxBoxRadius && sm::strip_path(a)) {
-        // frames past the separable path's limits (wider than 4096 columns): the strip kernel has none (the
-        // mirrored right view below takes it too)
-        SM_HIP(sm::launch_box_match_strip(a, batch, s));
     } else {
-        SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel, h->box_workgroups));
+        BoxRightOut ro;
+        // without the median the tile kernels match, form the right view and check in one pass over the partials
+        const bool one_pass = lr && !med && plan.left == sm::BoxLeft::Tile;
+        if (one_pass) {
+            ro.map = right_out;
+            ro.pitch = apitch;
+            ro.stride = astride;
+            ro.check = 1;
+            ro.mask = mask_out;
+        } else if (lr) {
+            ro.map = right_map;
+            ro.pitch = W;
+            ro.stride = P;
+        }
+        ro.mirror = mirror;
+        int rc = run_box_pass(ws, h, a, batch, plan, ro);
+        if (rc || one_pass) return rc;
     }
     if (med) SM_HIP(sm::launch_median(left_raw, W, H, W, P, batch, kMedianRadius, disp, opitch, ostride, s));
     if (!lr) return SM_OK;
 
-    // ---- right map on the mirrored pair (StereoHelper.cpp:156-180 + :131-154), box r > 7 ----
-    if (mirrored) {
-        SM_HIP(sm::launch_mirror(R, W, H, pitch, fstride, batch, mL, W, P, s));
-        SM_HIP(sm::launch_mirror(L, W, H, pitch, fstride, batch, mR, W, P, s));
-        {
-            sm::MatchArgs b = a;
-            b.left = mL;
-            b.right = mR;
-            b.pitch = W;
-            b.frame_stride = P;
-            b.valid_mode = 1;
-            b.seed_key = 0xFFFFFFFFu;
-            b.thresh_key = 0xFFFFFFFFu;
-            b.disp = right_map;
-            b.out_pitch = W;
-            b.out_frame_stride = P;
-            if (radius > sm::kMaxBoxRadius && sm::strip_path(b))   // frames wider than the separable path takes
-                SM_HIP(sm::launch_box_match_strip(b, batch, s));
-            else
-                SM_HIP(sm::launch_box_match(b, batch, s));
-        }
-    }
     const uint8_t* rcheck = right_map;
     if (med) {   // the median commutes with the mirror, so a mirrored map is filtered as is
         SM_HIP(sm::launch_median(right_map, W, H, W, P, batch, kMedianRadius, right_med, W, P, s));

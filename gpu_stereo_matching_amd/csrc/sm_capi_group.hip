@@ -173,15 +173,18 @@ int dslice_member_upload(sm_handle* h, int k, int n, const uint8_t* left, const 
     int rc = h->dsl.reserve(dslice_ws(nullptr, p, n, c.W, c.lr).bytes);
     if (rc) return rc;
     // what the key pass will take from the shared workspaces is sized here too, so that no allocation can fail
-    // after the pair all-gathers are enqueued: the wide path's V planes (a box slice at r 16..127,
-    // right keys included), or the right view's per-tile partials
+    // after the pair all-gathers are enqueued: exactly what the slice's box plan takes (none for the
+    // strip kernel without LR), or the guided right view's per-tile partials
     WsScope ws(h, s);
     uint8_t* unused = nullptr;
-    if (p.hi > p.lo && !c.guided && sm::wide_path(c.radius, c.W, c.H, c.W))
-        rc = ws.get(h->vol, sm::wide_workspace_bytes(c.W, c.H, p.hi - p.lo, 1), &unused);
-    else if (p.hi > p.lo && c.lr)
-        rc = ws.get(h->rpart, c.guided ? sm::guided_right_partial_bytes(c.W, c.H, c.radius, p.hi - p.lo, 1)
-                                       : sm::box_right_partial_bytes(c.W, c.H, c.radius, p.hi - p.lo, 1), &unused);
+    if (p.hi > p.lo && !c.guided) {
+        const sm::BoxPlan plan = sm::plan_box_pass({c.W, c.H, c.W, c.radius, p.lo, p.hi, 1},
+                                                   c.lr ? sm::RightWant::Keys : sm::RightWant::None);
+        if (plan.vol_bytes) rc = ws.get(h->vol, plan.vol_bytes, &unused);
+        if (!rc && plan.rpart_bytes) rc = ws.get(h->rpart, plan.rpart_bytes, &unused);
+    } else if (p.hi > p.lo && c.lr) {
+        rc = ws.get(h->rpart, sm::guided_right_partial_bytes(c.W, c.H, c.radius, p.hi - p.lo, 1), &unused);
+    }
     if (rc) return rc;
     const DsliceWs w = dslice_ws(h->dsl.p, p, n, c.W, c.lr);
     rc = dslice_upload_rows(p, w, k, left, right, c.W, pitch, s);

@@ -16,8 +16,8 @@ constexpr uint32_t kNoRightKey = 0x7FFFFFFFu;
 
 // The slice pass over [d_lo, d_hi) of frames already on the device (pitch `pitch`): left keys, and with
 // `rkeys` the right view's keys from the same fused pass (its per-tile partials in the handle's rpart
-// workspace).  Keys are [H][W]; no padding.  radius > 15 runs the wide-window path through the handle's volume
-// workspace; a pass that takes neither workspace stays outside the scope's ordering.
+// workspace).  Keys are [H][W]; no padding.  The box kernels and their workspaces are plan_box_pass's
+// (bm_box_plan.h); a pass that takes no workspace stays outside the scope's ordering.
 int slice_keys_pass(WsScope& ws, sm_handle* h, const uint8_t* dL, const uint8_t* dR, int W, int H, int pitch,
                     int radius, int d_lo, int d_hi, bool guided, uint32_t* keys, uint32_t* rkeys) {
     hipStream_t s = ws.stream();
@@ -48,25 +48,12 @@ int slice_keys_pass(WsScope& ws, sm_handle* h, const uint8_t* dL, const uint8_t*
     a.seed_key = seed_key(radius);
     a.thresh_key = seed_key(radius);
     a.keys = keys;
-    if (!rkeys && sm::strip_path(a)) {   // r 16..37: the strip kernel (bm_strip.hip), at any width
-        SM_HIP(sm::launch_box_match_strip(a, 1, s));
-        return SM_OK;
-    }
-    if (sm::wide_path(radius, W, H, pitch)) {   // r 16..127: the wide path (bm_wide.hip), right keys sign-flipped
-        uint16_t* v = nullptr;
-        int rc = ws.get(h->vol, sm::wide_workspace_bytes(W, H, d_hi - d_lo, 1), &v);
-        if (rc) return rc;
-        SM_HIP(sm::launch_box_match_wide(a, 1, v, nullptr, 0, 0, s, rkeys));
-        return SM_OK;
-    }
-    if (!rkeys) {
-        SM_HIP(sm::launch_box_match(a, 1, s, h->box_kernel, h->box_workgroups));
-        return SM_OK;
-    }
-    int rc = ws.get(h->rpart, sm::box_right_partial_bytes(W, H, radius, d_hi - d_lo, 1), &a.rpart);
-    if (rc) return rc;
-    SM_HIP(sm::launch_box_slice_lr_keys(a, 1, rkeys, s));
-    return SM_OK;
+    // (right keys from the wide path are sign-flipped, kRightKeyFlip)
+    const sm::BoxPlan plan =
+        sm::plan_box_pass({W, H, pitch, radius, d_lo, d_hi, 1}, rkeys ? sm::RightWant::Keys : sm::RightWant::None);
+    BoxRightOut ro;
+    ro.keys = rkeys;
+    return run_box_pass(ws, h, a, 1, plan, ro);
 }
 
 int slice_check(int d_lo, int d_hi) {
@@ -100,7 +87,8 @@ int dslice_check(const DsliceCfg& c, unsigned flags) {
                     "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK; no median, staged)", flags);
     if (c.guided && c.radius > sm::kMaxFastRadius)
         return fail(SM_ERR_INVALID_ARG, "guided aggregation: radius %d > %d", c.radius, sm::kMaxFastRadius);
-    if (c.lr && !c.guided && c.radius > sm::kMaxBoxRadius && !sm::wide_path(c.radius, c.W, c.H, c.W))
+    if (c.lr && !c.guided &&
+        sm::plan_box_pass({c.W, c.H, c.W, c.radius, 0, c.D, 1}, sm::RightWant::Keys).right == sm::BoxRight::Unsupported)
         return fail(SM_ERR_INVALID_ARG, "d-slice LR: box radius %d > %d needs the wide path (width <= %d)", c.radius,
                     sm::kMaxBoxRadius, sm::kMaxWideWidth);
     return SM_OK;
@@ -234,8 +222,10 @@ SM_API int sm_slice_keys_lr_device(sm_handle* h, const uint8_t* d_left, const ui
     if ((flags & ~(unsigned)SM_AGG_GUIDED) != 0u)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: flags 0x%x (SM_AGG_BOX or SM_AGG_GUIDED)", flags);
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
+    // (whether box right keys exist does not depend on the slice, which is checked below)
     if (guided ? radius > sm::kMaxFastRadius
-               : radius > sm::kMaxBoxRadius && !sm::wide_path(radius, width, height, pitch))
+               : sm::plan_box_pass({width, height, pitch, radius, 0, 1, 1}, sm::RightWant::Keys).right ==
+                     sm::BoxRight::Unsupported)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: radius %d > %d%s", radius,
                     guided ? sm::kMaxFastRadius : sm::kMaxBoxRadius,
                     guided ? "" : " outside the wide path (width 4..4096, frame < 2^31 bytes)");

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/sm_hip.h"
+#include "bm_box_plan.h"
 #include "bm_common.h"
 #include "bm_guided.h"
 #include "bm_segtree.h"
@@ -247,6 +248,25 @@ struct VolumeOut {
 // SM_AGG_SGM, SM_COST_CENSUS and the sub-pixel calls (sm_capi_volume.hip)
 int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
                int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const VolumeOut& o);
+
+// ---- the box pass (sm_capi.hip) ----
+// Where the right view of a box pass goes, by what the plan was asked for.
+struct BoxRightOut {
+    // RightWant::Map: dR [batch][H][pitch], dense (pitch W, stride W * H) unless `check`; stored mirrored when the
+    // plan's right view is Mirrored
+    uint8_t* map = nullptr;
+    int pitch = 0;
+    int64_t stride = 0;
+    // Tile / Fused only: 1 applies the LR check in the same pass (launch_box_match_lr: a.disp receives the checked
+    // map; `map` and `mask`, the valid mask, are optional)
+    int check = 0;
+    uint8_t* mask = nullptr;
+    uint32_t* keys = nullptr;    // RightWant::Keys: the slice's right keys [batch][H][W]
+    uint8_t* mirror = nullptr;   // plan.mirror_planes dense planes of W * H * batch bytes
+};
+// Issues the launches of plan p = plan_box_pass(a's geometry and batch, what `r` receives): the left pass into
+// a.disp / a.keys, the right view into `r`.  The plan's workspaces are taken from the handle through ws, each once.
+int run_box_pass(WsScope& ws, sm_handle* h, sm::MatchArgs a, int batch, const sm::BoxPlan& p, const BoxRightOut& r);
 
 // Host-pointer pass over one frame (or one row band of a frame: sm_group_*; sm_capi.hip).  Only result rows
 // [keep0, keep1) are downloaded, into disp_out / right_out / mask_out pointing at row keep0.

@@ -245,3 +245,47 @@ def test_wide_path_tiny_frames(matcher, oracle, W, H):
         chk, rd, mask = matcher.match_lr(L, R, 16, D)
         _, rd_o, chk_o, mask_o = oracle.box_lr(L, R, 16, D)
         assert np.array_equal(rd, rd_o) and np.array_equal(chk, chk_o) and np.array_equal(mask, mask_o), D
+
+
+# ---- the frames neither the strip kernel nor the wide path takes: the direct kernel (bm_box_plan.h) ----
+
+@pytest.fixture(scope="module")
+def past_wide(sm, oracle):
+    """A pair wider than the wide path's 4096 columns, and a handle for it."""
+    L, R = oracle.synth_pair(9, 4100, 6, 16)
+    with sm.BlockMatcher(0, 4100, 8, 16) as m:
+        yield m, L, R
+
+
+def test_direct_kernel_mirrored_right_view(past_wide, oracle):
+    """r = 40 past 4096 columns: the left map and the mirrored pair's right view both on the direct kernel."""
+    m, L, R = past_wide
+    chk, rd, mask = m.match_lr(L, R, 40, 5)
+    _, rd_o, chk_o, mask_o = oracle.box_lr(L, R, 40, 5)
+    assert np.array_equal(rd, rd_o) and np.array_equal(chk, chk_o) and np.array_equal(mask, mask_o)
+
+
+@pytest.mark.parametrize("W,H,r,D", [(3, 5, 16, 4), (3, 5, 40, 4), (2, 1, 16, 3)])
+def test_direct_kernel_frames_under_4_columns(matcher, oracle, W, H, r, D):
+    """W < 4 at r >= 16: below the dword loads of the strip kernel and the wide path."""
+    rng = np.random.default_rng(1000 * W + 10 * H + r)
+    L = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    R = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    assert np.array_equal(matcher.match(L, R, r, D), oracle.box_disp(L, R, r, D))
+    chk, rd, mask = matcher.match_lr(L, R, r, D)
+    _, rd_o, chk_o, mask_o = oracle.box_lr(L, R, r, D)
+    assert np.array_equal(rd, rd_o) and np.array_equal(chk, chk_o) and np.array_equal(mask, mask_o)
+
+
+def test_direct_kernel_slice_keys(sm, past_wide, oracle):
+    """Slice keys past 4096 columns at r = 40: the left keys from the direct kernel; the right view's keys exist
+    on the wide path only, and the call says so."""
+    import torch
+    m, L, R = past_wide
+    Lt, Rt = torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()
+    k = m.slice_keys_device(Lt, Rt, 40, 1, 4)
+    torch.cuda.synchronize()
+    assert np.array_equal(k.cpu().numpy().view(np.uint32), oracle.box_keys_slice(L, R, 40, 1, 4))
+    with pytest.raises(sm.SMError, match=r"slice LR keys: radius 40 > 15 outside the wide path \(width 4\.\.4096, "
+                                         r"frame < 2\^31 bytes\)"):
+        m.slice_keys_lr_device(Lt, Rt, 40, 1, 4)

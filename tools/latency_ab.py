@@ -1,7 +1,7 @@
-"""Batch-1 latency of the plain box matcher under build/env switches, one process per setting (the
+"""Batch-1 latency of the plain box matcher under environment settings, one process per setting (the
 switches are read at the first launch): 1080p, 960x540, 640x480, 463x370 and 320x240 frames, device resident,
 50 back-to-back calls, HIP events; each map is checked against the first setting's.
-usage: python tools/latency_ab.py "SM_WIDE_TILES=0" "SM_WIDE_TILES=1" ..."""
+usage: python tools/latency_ab.py "NAME=0" "NAME=1 OTHER=2" ...   (at least one setting; each a list of NAME=value)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = r"""
@@ -24,7 +24,9 @@ for (W, H, D, r) in ((1920, 1080, 128, 5), (463, 370, 64, 4), (640, 480, 64, 5),
 import tempfile
 import numpy as np
 td = tempfile.mkdtemp()
-settings = sys.argv[1:] or ["SM_WIDE_TILES=0", "SM_WIDE_TILES=1"]
+settings = sys.argv[1:]
+if not settings:
+    sys.exit(__doc__)
 for i, st in enumerate(settings):
     env = dict(os.environ)
     for kv in st.split():
