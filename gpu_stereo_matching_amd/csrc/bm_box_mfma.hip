@@ -11,7 +11,8 @@
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
 // A workgroup walks a contiguous range of tiles; along a row of tiles it keeps the right band in LDS and stages
 // only the new columns.  The unmasked paired loop is written slot by slot, every MFMA between vector
-// work of its own wave (run_paired).
+// work of its own wave (run_paired), and carries its key constants and R addresses from pass to pass
+// (DESIGN §26).
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -188,7 +189,8 @@ template <int R, int DMAX, int NP, bool WALK>
 __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, int tiles_y, int per, int rem) {
     using G = MG<R, DMAX, NP>;
     constexpr int NXB = G::NXB, NOB = G::NOB;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    // (aligned to 16 columns, the period of slot()'s swizzle in the address)
+    extern __shared__ __attribute__((aligned(16 * kColB))) uint8_t smem[];
     uint8_t* lsm = smem;                  // [64][64] f16, swizzled
     uint8_t* rsm = smem + G::L_BYTES;     // [RC][64] f16, swizzled
 
@@ -434,36 +436,73 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         auto run_paired = [&](auto np_c, const int lo, const int hi) {
             static_assert(decltype(np_c)::value == 2 && NOB == 3, "the paired loop");
             auto slot_end = [] { __builtin_amdgcn_sched_barrier(0); };
+            // An empty asm that takes a value and gives it back (no instruction is emitted).  In a slot: a value that
+            // only the next pass reads is computed there, not at the loop's end.  At the head of a pass: a value that
+            // does not change stays in its registers and what is read through it stays in the loop
+            auto pin = [](auto& v) { asm volatile("" : "+v"(v)); };
             // the two keys of a pixel against its best: v_min3_u32
             auto mins = [&](int ob, int x, const u4& o0, const u4& o1) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) best[ob][x][i] = min(best[ob][x][i], min(o0[i], o1[i]));
             };
+            // Carried from pass to pass, stepped in the last output block's slots instead of rebuilt at the head of a
+            // pass, ahead of its first reads:
+            //   c2[p]   the key constant of disparity d + p as a splat, + 2.0 per pass.  The odd last pass repeats
+            //           d = hi - 1 as p = 1 (dd[1]) and labels it d + 1: the same cost as p = 0's key with a larger low
+            //           byte, so it loses every min against p = 0's key and changes nothing
+            //   rcol    byte offset of p = 0's column l16 + DMAX + d_lo - d, - 2 columns per pass.  slot()'s swizzle
+            //           (col >> 1) & 7 is bits 8..10 of it, so an address is a shift, an and-xor and an add
+            //   raddr[] the two R addresses of the pass; p = 1 reads one column to the left, or p = 0's in an odd
+            //           last pass (dd[] decides, as it does in run())
+            // The addresses are LDS addresses, not offsets into smem[] to which every read adds the array's own
+            // address again: smem is aligned to a whole swizzle period, so the swizzle of an address is the swizzle
+            // of the offset
+            const int g16 = g << 4;
+            auto swz = [&](int colb) { return colb + (((colb >> 4) & 0x70) ^ g16); };
+            auto lds_u4 = [](int addr) { return *(const __attribute__((address_space(3))) u4*)(uint32_t)addr; };
+            const int lds0 = (int)(uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)smem;
+            auto raddr_at = [&](int colb, int d, int (&ra)[2]) {
+                ra[0] = swz(colb);
+                ra[1] = swz(colb - (d + 1 < hi ? kColB : 0));
+            };
+            int rcol = lds0 + G::L_BYTES + (l16 + DMAX + d_lo - lo) * kColB;
+            int raddr[2];
+            raddr_at(rcol, lo, raddr);
+            f4 c2[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const float c2v = c2base + (float)(lo + p);
+                c2[p] = f4{c2v, c2v, c2v, c2v};
+            }
+            const f4 two = {2.0f, 2.0f, 2.0f, 2.0f};
+            // L does not depend on d, and as in run() its reads stay inside the loop, once per pair: here the two
+            // chunk addresses pass through an empty asm per pass instead of a d-dependent zero
+            int laddr_c[2] = {lds0 + laddr, (lds0 + laddr) ^ 64};
+            // stage 1's C operand, held: left to the compiler it is rebuilt from scalar registers in every pass
+            f4 c1p = c1;
 #pragma unroll 1
             for (int d = lo; d < hi; d += 2) {
-                const int dd[2] = {d, min(d + 1, hi - 1)};
-                int raddr[2];
-                f4 c2[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    raddr[p] = slot(l16 + DMAX + d_lo - dd[p], g);
-                    const float c2v = c2base + (float)dd[p];
-                    c2[p] = f4{c2v, c2v, c2v, c2v};
-                }
-                const int laddr_d = laddr + (int)((uint32_t)d >> 31);   // as in run(): L is read once per pair
+                pin(laddr_c[0]);
+                pin(laddr_c[1]);
+                pin(c1p);
                 u4 t[2][NOB];
                 u4 lq[2], rq[2][2];   // [chunk], [p][chunk] of the block whose reads are out
                 // the reads of 32-row chunk c of column block cb
-                auto fetch_l = [&](int cb, int c) {
-                    lq[c] = *reinterpret_cast<const u4*>(lsm + (laddr_d ^ (64 * c)) + cb * 16 * kColB);
-                };
+                auto fetch_l = [&](int cb, int c) { lq[c] = lds_u4(laddr_c[c] + cb * 16 * kColB); };
                 auto fetch_r = [&](int cb, int p, int c) {
-                    rq[p][c] = *reinterpret_cast<const u4*>(rsm + (raddr[p] ^ (64 * c)) + cb * 16 * kColB);
+                    rq[p][c] = lds_u4((raddr[p] ^ (64 * c)) + cb * 16 * kColB);
                 };
                 auto fetch = [&](int cb, int c) {
                     fetch_l(cb, c);
                     fetch_r(cb, 0, c);
                     fetch_r(cb, 1, c);
+                };
+                // the next pass's R addresses, once this pass's last R read is out
+                auto step_addr = [&] {
+                    rcol -= 2 * kColB;
+                    raddr_at(rcol, d + 2, raddr);
+                    pin(raddr[0]);
+                    pin(raddr[1]);
                 };
                 fetch(0, 0);
                 u4 om[2];   // stage 2 of the middle row block, carried to the next column block's first quad
@@ -499,27 +538,28 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         if (cb >= 2) mins(1, xb - 1, om[0], om[1]);
                         slot_end();
                         fetch_r(cb, 1, 1);
-                        sv[0][0] = mfma(ad[0][0], bv0, c1);
+                        sv[0][0] = mfma(ad[0][0], bv0, c1p);
                         half(1, 0, 0);
                         slot_end();
-                        sv[0][1] = mfma(ad[0][0], bvm, c1);
+                        sv[0][1] = mfma(ad[0][0], bvm, c1p);
                         half(1, 0, 1);
                         slot_end();
                         half(0, 1, 0);
+                        if (cb == NXB) step_addr();   // NXB = 3: the pass's last R read is out
                         slot_end();
-                        sv[1][0] = mfma(ad[1][0], bv0, c1);
+                        sv[1][0] = mfma(ad[1][0], bv0, c1p);
                         half(0, 1, 1);
                         slot_end();
-                        sv[1][1] = mfma(ad[1][0], bvm, c1);
+                        sv[1][1] = mfma(ad[1][0], bvm, c1p);
                         half(1, 1, 0);
                         slot_end();
-                        sv[0][2] = mfma(ad[0][1], bv0, c1);
+                        sv[0][2] = mfma(ad[0][1], bv0, c1p);
                         half(1, 1, 1);
                         slot_end();
                         sv[0][1] = mfma(ad[0][1], bvp, sv[0][1]);
                         cvt(0, 0);
                         slot_end();
-                        sv[1][2] = mfma(ad[1][1], bv0, c1);
+                        sv[1][2] = mfma(ad[1][1], bv0, c1p);
                         cvt(1, 0);
                         slot_end();
                         sv[1][1] = mfma(ad[1][1], bvp, sv[1][1]);
@@ -549,8 +589,10 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                             om[1] = o[1][1];
                         }
                     } else {
-                        // the last output block: both halves of t are there
+                        // the last output block: both halves of t are there; the next pass's addresses go under its
+                        // first MFMAs
                         stage2(0, 0);
+                        step_addr();
                         stage2(0, 1);
                         slot_end();
                         stage2(2, 0);
@@ -570,6 +612,9 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                     }
                 }
                 mins(1, NXB - 1, om[0], om[1]);
+                // (after the last MFMA that reads them: a write under it would wait for its C operand)
+                c2[0] += two;
+                c2[1] += two;
                 slot_end();
             }
         };
