@@ -10,9 +10,10 @@
 // tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
 // A workgroup walks a contiguous range of tiles; along a row of tiles it keeps the right band in LDS and stages
-// only the new columns.  The unmasked paired loop is written slot by slot, every MFMA between vector
-// work of its own wave (run_paired), and carries its key constants and R addresses from pass to pass
-// (DESIGN §26).
+// only the new columns.  The paired loop is written slot by slot, every MFMA between vector work of
+// its own wave (run_paired), and carries its key constants and R addresses from pass to pass (DESIGN
+// §26); a wave's masked passes are the same body plus the mask work, continuing where its unmasked passes end
+// (DESIGN §27).  run() is the loop of the one-d-per-pass kernels alone.
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -309,15 +310,15 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                 for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)i * a.pitch, 4);
             }
         };
-        // NP = 1: before the disparity loops, which cover the latency.  NP = 2: after the unmasked loop, whose order
-        // needs the eight registers; the masked loop, the fold and the epilogue are between the loads
-        // and their use
+        // NP = 1: before the disparity loops, which cover the latency.  NP = 2: after both loops, whose order needs
+        // the eight registers; the fold and the epilogue are between the loads and their use
         if constexpr (NP == 1) issue_prefetch();
 
         __syncthreads();
 
-        // one loop over [lo, hi); MASKED: with the c >= d and c < W mask of the staged columns and the d <= W - x
-        // mask of the outputs
+        // One loop over [lo, hi) in the compiler's order; MASKED: with the c >= d and c < W mask of the staged columns
+        // and the d <= W - x mask of the outputs.  The NP = 1 kernels run it for both parts of a wave's range; the
+        // NP = 2 kernels do not instantiate it (run_paired below), its NP = 2 arms state the same arithmetic
         auto run = [&](auto masked_c, const int lo, const int hi) {
             constexpr bool MASKED = decltype(masked_c)::value;
             // NP = 2: two disparities per pass; an odd range ends with its last d twice (the same keys: min3 is
@@ -418,7 +419,7 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                 }
             }
         };
-        // The unmasked loop of two disparities per pass, the same arithmetic as run() in an order that gives every
+        // The loops of two disparities per pass, the same arithmetic as run() in an order that gives every
         // MFMA vector work of its own wave that does not wait for it.  A column block is a sequence of
         // slots, one MFMA and two to four vector instructions each, a scheduling barrier after every slot, so the source
         // order is the machine order:
@@ -431,9 +432,22 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         //             done; the mins of the middle row block wait for the first AD quad of the next column block
         //   reads     chunk 0 of the next block goes out before the last three stage-2 MFMAs, chunk 1 with the
         //             block's first quad (the R read its last quad needs one slot later), so only the first block of
-        //             a pass begins with a wait.  Reading all six ahead, or holding the next tile's staging loads
-        //             over this loop as NP = 1 does, does not fit in 168 registers
-        auto run_paired = [&](auto np_c, const int lo, const int hi) {
+        //             a pass begins with a wait (sending that block's reads out from the pass before was measured and
+        //             bought nothing).  Reading all six ahead, or holding the next tile's staging loads
+        //             over these loops as NP = 1 does, does not fit in 168 registers
+        // Both loops of a wave are this one body, [lo, mid) unmasked and [mid, hi) masked: the masked
+        // instantiation is the unmasked one plus the mask work, and takes over the carried values where the first
+        // loop leaves them (mid - lo is even).
+        //   AD mask   keep = kAbsBits or 0 per (column block, p) from d <= c < W as one unsigned compare of
+        //             l16 + c0 against W - d, both scalars carried and stepped by -2 per pass; made ahead of the
+        //             block's first quad, in the slots of the second and third stage-2 MFMA of the block to the left
+        //             (the first block's at the head of the pass, behind its reads)
+        //   key mask  element i of output block xb is valid for d <= W - x, i.e. 4 i <= e4 for p = 0 and
+        //             4 (i + 1) <= e4 for p = 1 with the one per-lane operand e4 = 4 (W - x0 - 16 xb - d) - 16 g; made
+        //             from the carried c2[p] in the two slots before the block's stage 2, under stage-1 MFMAs, which
+        //             do not read it (in the last output block, which has no stage 1, ahead of its first two MFMAs)
+        // In an odd last pass p = 1 repeats d: its masks are p = 0's (`one` is 0), as its R address is
+        auto run_paired = [&](auto np_c, const int lo, const int mid, const int hi) {
             static_assert(decltype(np_c)::value == 2 && NOB == 3, "the paired loop");
             auto slot_end = [] { __builtin_amdgcn_sched_barrier(0); };
             // An empty asm that takes a value and gives it back (no instruction is emitted).  In a slot: a value that
@@ -480,11 +494,21 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             int laddr_c[2] = {lds0 + laddr, (lds0 + laddr) ^ 64};
             // stage 1's C operand, held: left to the compiler it is rebuilt from scalar registers in every pass
             f4 c1p = c1;
-#pragma unroll 1
-            for (int d = lo; d < hi; d += 2) {
+            // The masks' scalars: wd = W - d, c0s = x0 - R - d, the image column of lane 0's staged column less d.  They
+            // pass through an empty asm in every pass, so that nothing per-lane is derived from them ahead of the loop
+            // and held over it
+            int wd = W - mid, c0s = x0 - R - mid;
+            auto pass = [&](auto masked_c, const int d) {
+                constexpr bool MASKED = decltype(masked_c)::value;
                 pin(laddr_c[0]);
                 pin(laddr_c[1]);
                 pin(c1p);
+                // 1 where p = 1 is d + 1, 0 where it repeats d (the odd last pass)
+                const int one = d + 1 < hi ? 1 : 0;
+                if constexpr (MASKED) {
+                    asm volatile("" : "+s"(wd));
+                    asm volatile("" : "+s"(c0s));
+                }
                 u4 t[2][NOB];
                 u4 lq[2], rq[2][2];   // [chunk], [p][chunk] of the block whose reads are out
                 // the reads of 32-row chunk c of column block cb
@@ -497,14 +521,32 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                     fetch_r(cb, 0, c);
                     fetch_r(cb, 1, c);
                 };
-                // the next pass's R addresses, once this pass's last R read is out
+                uint32_t keep[2] = {kAbsBits, kAbsBits};
+                f4 c2x[2];
+                auto mk_keep = [&](int cb, int p) {
+                    if constexpr (MASKED)
+                        keep[p] = (uint32_t)(l16 + (c0s + 16 * cb - p * one)) < (uint32_t)(wd - p * one) ? kAbsBits : 0u;
+                };
+                auto mk_c2x = [&](int xb, int p) {
+                    if constexpr (MASKED) {
+                        const int e4 = 4 * (wd - x0 - 16 * xb) - g16;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            c2x[p][i] = 4 * (i + p * one) <= e4 ? c2[p][0] : __builtin_bit_cast(float, kInfBits);
+                    }
+                };
+                // the next pass's R addresses, once this pass's last R read is out (the unmasked loop's last pass steps
+                // to `mid`, the masked loop's first).  The step is a scalar, 0 in the range's last pass, whose addresses
+                // nobody reads: with a literal step the slot compiles to one instruction and six wait states more
                 auto step_addr = [&] {
-                    rcol -= 2 * kColB;
+                    rcol -= d + 2 < hi ? 2 * kColB : 0;
                     raddr_at(rcol, d + 2, raddr);
                     pin(raddr[0]);
                     pin(raddr[1]);
                 };
                 fetch(0, 0);
+                mk_keep(0, 0);
+                mk_keep(0, 1);
                 u4 om[2];   // stage 2 of the middle row block, carried to the next column block's first quad
 #pragma unroll
                 for (int cb = 0; cb <= NXB; ++cb) {
@@ -519,7 +561,7 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         for (int m = 2 * h; m < 2 * h + 2; ++m) {
                             const uint32_t lm = lq[c][m], rm = rq[p][c][m];
                             const h2 df = __builtin_bit_cast(h2, lm) - __builtin_bit_cast(h2, rm);
-                            ad[p][c][m] = __builtin_bit_cast(uint32_t, df) & kAbsBits;
+                            ad[p][c][m] = __builtin_bit_cast(uint32_t, df) & keep[p];
                         }
                     };
                     auto cvt = [&](int p, int ob) {
@@ -528,7 +570,7 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         t[p][ob][2 * (cb & 1) + 1] = pk.y;
                     };
                     auto stage2 = [&](int ob, int p) {
-                        o[p][ob] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], c2[p]));
+                        o[p][ob] = __builtin_bit_cast(u4, mfma((cb & 1) ? bh : bhs, t[p][ob], MASKED ? c2x[p] : c2[p]));
                     };
                     if (s1) {
                         fetch_l(cb, 1);
@@ -558,9 +600,11 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         slot_end();
                         sv[0][1] = mfma(ad[0][1], bvp, sv[0][1]);
                         cvt(0, 0);
+                        if (s2) mk_c2x(xb, 0);
                         slot_end();
                         sv[1][2] = mfma(ad[1][1], bv0, c1p);
                         cvt(1, 0);
+                        if (s2) mk_c2x(xb, 1);
                         slot_end();
                         sv[1][1] = mfma(ad[1][1], bvp, sv[1][1]);
                         cvt(0, 2);
@@ -570,9 +614,11 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         slot_end();
                         if (s2) stage2(0, 1);
                         cvt(1, 2);
+                        if (cb + 1 < 4) mk_keep(cb + 1, 0);
                         slot_end();
                         if (s2) stage2(2, 0);
                         cvt(1, 1);
+                        if (cb + 1 < 4) mk_keep(cb + 1, 1);
                         slot_end();
                         if (cb + 1 < 4) fetch(cb + 1, 0);
                         if (s2) {
@@ -591,8 +637,10 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                     } else {
                         // the last output block: both halves of t are there; the next pass's addresses go under its
                         // first MFMAs
+                        mk_c2x(xb, 0);
                         stage2(0, 0);
                         step_addr();
+                        mk_c2x(xb, 1);
                         stage2(0, 1);
                         slot_end();
                         stage2(2, 0);
@@ -615,11 +663,19 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                 // (after the last MFMA that reads them: a write under it would wait for its C operand)
                 c2[0] += two;
                 c2[1] += two;
+                if constexpr (MASKED) {
+                    wd -= 2;
+                    c0s -= 2;
+                }
                 slot_end();
-            }
+            };
+#pragma unroll 1
+            for (int d = lo; d < mid; d += 2) pass(std::false_type{}, d);
+#pragma unroll 1
+            for (int d = mid; d < hi; d += 2) pass(std::true_type{}, d);
         };
         if constexpr (NP == 2) {
-            run_paired(std::integral_constant<int, NP>{}, dw_lo, dw_m);
+            run_paired(std::integral_constant<int, NP>{}, dw_lo, dw_m, dw_hi);
             // (zeros on the other path: an undefined value would be taken as last tile's and held over the loop)
             if (!prefetch) {
 #pragma unroll
@@ -628,8 +684,8 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             issue_prefetch();
         } else {
             run(std::false_type{}, dw_lo, dw_m);
+            run(std::true_type{}, dw_m, dw_hi);
         }
-        run(std::true_type{}, dw_m, dw_hi);
 
         __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
 
