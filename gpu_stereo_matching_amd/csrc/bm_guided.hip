@@ -560,7 +560,7 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
         for (int k = 0; k < G::SW1 + 2 * R; ++k) v[k] = row[k];
 #if SM_G_ACC
         // SM_G_ACC: the packed column sums are summed as they are (acc, wrapping u32) beside the exact Sp; the
-        // window's SIp < 2^23 is then acc - Sp * 2^20 (mod 2^32, exact), one v_mad_i32_i24 per output instead of
+        // window's SIp < 2^24 is then acc - Sp * 2^20 (mod 2^32, exact), one v_mad_i32_i24 per output instead of
         // an and + add per column
         uint32_t sp = 0, acc = 0;
 #pragma unroll
@@ -587,12 +587,20 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
             sp += v[o + 2 * R] >> 20;
             sip += v[o + 2 * R] & k_plow;
 #endif
-            // N*SIp - SI*Sp = N^2 cov(I, p), |.| < 2^30, exactly: every factor fits a signed 24-bit
-            // operand (SIp <= 121 * 255^2 < 2^23), so v_mul_i32_i24 + v_mad_i32_i24 (written out: the
-            // compiler otherwise turns one product into a quarter-rate v_mul_lo_u32)
+            // N*SIp - SI*Sp = N^2 cov(I, p), |.| < 2^30, exactly (mod 2^32), from 24-bit products (written out:
+            // the compiler otherwise turns one product into a quarter-rate v_mul_lo_u32).  -SI and Sp fit
+            // signed 24-bit operands at every radius.  SIp <= (2R+1)^2 * 255^2 does up to r = 5 (121 * 255^2
+            // < 2^23); at r = 6, 7 it passes 2^23 on bright guides with large costs (< 2^24 = the unsigned
+            // operand's range), where v_mad_i32_i24 read it as SIp - 2^24 and a and b came out far off
+            // (tests/test_gpu_guided_cost.py): those radii take v_mad_u32_u24, the same low 32 bits otherwise
+            constexpr bool kSIpSigned = (2 * R + 1) * (2 * R + 1) * 255 * 255 < (1 << 23);
+            static_assert((2 * R + 1) * (2 * R + 1) * 255 * 255 < (1 << 24), "SIp fits an unsigned 24-bit operand");
             int32_t num;
             asm("v_mul_i32_i24 %0, %1, %2" : "=v"(num) : "v"(nSI[o]), "v"(sp));
-            asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(num) : "v"(nN[o]), "v"(sip));
+            if constexpr (kSIpSigned)
+                asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(num) : "v"(nN[o]), "v"(sip));
+            else
+                asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(num) : "v"(nN[o]), "v"(sip));
             const float a = (float)num * invden[o];
             // float(Sp) without v_cvt (a quarter-rate op here): Sp < 2^22, float(2^23 + Sp) is exact
             const float fsp = __builtin_bit_cast(float, k_magic | sp) + k_magicf;

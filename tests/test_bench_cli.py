@@ -61,7 +61,12 @@ def test_plain_run_times_its_steps_and_dumps_the_last_map(tmp_path, oracle):
     assert res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
     assert res["unit"] == "disparity-maps/s" and res["higher_is_better"] is True and res["dtype"] == "u8"
     assert res["ms_per_step"] > 0
-    assert res["value"] == pytest.approx(B * 1000.0 / res["ms_per_step"], rel=1e-3)
+    # the line prints ms_per_step to 4 decimals (half a unit is 0.2 % of a 26 us step, more than the 1e-3 asked
+    # of the value): the value agrees to 1e-3 with some step time that prints as this one
+    half = 0.5e-4
+    assert res["ms_per_step"] > half
+    assert res["value"] >= B * 1000.0 / (res["ms_per_step"] + half) * (1 - 1e-3)
+    assert res["value"] <= B * 1000.0 / (res["ms_per_step"] - half) * (1 + 1e-3)
     # nothing beside the headline in a plain run
     for key in ("variants", "cfg5_guided_lr", "cfg3_guided", "staged_hbm_roofline", "dslice", "rowband"):
         assert key not in res
