@@ -132,23 +132,6 @@ static_assert(Geo<1, 128, 8>::LDS_BYTES_R <= 81920 && Geo<5, 128, 8>::LDS_BYTES_
 static_assert(Geo<1, 192, 6>::LDS_BYTES_R <= 81920 && Geo<5, 192, 6>::LDS_BYTES_R <= 81920,
               "right view d_max 192: 2 workgroups per CU (r = 6 needs 82.7 KB, one)");
 
-// 4 image bytes of row y from column x (little-endian), bytes outside the image read as 0.
-// Interior dwords are one (possibly unaligned) global_load_dword; border dwords go byte-wise.
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p, int y, int x, int W, int H, int pitch) {
-    if (y < 0 || y >= H) return 0u;
-    const uint8_t* row = p + (int64_t)y * pitch;
-    if (x >= 0 && x + 3 < W) {
-        uint32_t v;
-        __builtin_memcpy(&v, row + x, 4);
-        return v;
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
-    return v;
-}
-
 // v_perm_b32 selectors building the v_sad operands from w = R(c-d) | R(c-d-1) << 8 and the packed
 // left column word lq (L of rows 4q..4q+3 in bytes 0..3); pool byte 0-3 = lq, 4-7 = w:
 //   A = [L, R(c-d-1), 0, 0]  -> sad_u8(A, w)    = |L - R(c-d)|
@@ -235,8 +218,8 @@ void box_match_kernel(MatchArgs a, int tiles_x, int tiles_y) {
         for (int e = tid; e < NR; e += kThreads) {
             const int i = e / G::NDW, j = e - (e / G::NDW) * G::NDW;
             const int y = y0 - R + i, col = base + 4 * j;
-            const uint32_t cur = ld_u32(Rf, y, col, W, H, a.pitch);
-            const uint32_t prv = ld_u32(Rf, y, col - 4, W, H, a.pitch);
+            const uint32_t cur = ld_image_u32(Rf, y, col, W, H, a.pitch);
+            const uint32_t prv = ld_image_u32(Rf, y, col - 4, W, H, a.pitch);
             uint2 v;
             v.x = __builtin_amdgcn_perm(cur, prv, 0x04050304u);
             v.y = __builtin_amdgcn_perm(cur, cur, 0x06070506u);
@@ -244,7 +227,8 @@ void box_match_kernel(MatchArgs a, int tiles_x, int tiles_y) {
         }
         for (int e = tid; e < NL; e += kThreads) {
             const int i = e / (G::LSTR / 4), j = e - (e / (G::LSTR / 4)) * (G::LSTR / 4);
-            *reinterpret_cast<uint32_t*>(ls + i * G::LSTR + 4 * j) = ld_u32(Lf, y0 - R + i, lbase + 4 * j, W, H, a.pitch);
+            *reinterpret_cast<uint32_t*>(ls + i * G::LSTR + 4 * j) =
+                ld_image_u32(Lf, y0 - R + i, lbase + 4 * j, W, H, a.pitch);
         }
     }
     __syncthreads();

@@ -92,22 +92,6 @@ struct MG {
 // byte offset of 16-B row group q (rows 8q..8q+7) of staged column `col`
 __device__ __forceinline__ int slot(int col, int q) { return col * kColB + ((q ^ ((col >> 1) & 7)) << 4); }
 
-// 4 image bytes of row y from column x (little-endian), bytes outside the image read as 0
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p, int y, int x, int W, int H, int pitch) {
-    if (y < 0 || y >= H) return 0u;
-    const uint8_t* row = p + (int64_t)y * pitch;
-    if (x >= 0 && x + 3 < W) {
-        uint32_t v;
-        __builtin_memcpy(&v, row + x, 4);
-        return v;
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
-    return v;
-}
-
 // eight rows of one element (4 columns x 8 rows) as f16 1024 + v into columns `col`.. of row group q
 __device__ __forceinline__ void stage_pack(const uint32_t (&w)[8], uint8_t* dst, int col, int q) {
 #pragma unroll
@@ -128,7 +112,7 @@ __device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xle
         const int q = e / NC4, j = e - q * NC4;
         uint32_t w[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = ld_u32(img, ytop + 8 * q + i, xleft + 4 * j, W, H, pitch);
+        for (int i = 0; i < 8; ++i) w[i] = ld_image_u32(img, ytop + 8 * q + i, xleft + 4 * j, W, H, pitch);
         stage_pack(w, dst, 4 * j, q);
     }
 }
@@ -762,7 +746,7 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         if (!prefetch) {   // an edge tile: the guarded loads, now
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                pw[i] = ld_u32(ce.right ? Rf : Lf, y0 - R + 8 * ce.q + i, (ce.right ? nxr : nxl) + ce.dx, W, H,
+                pw[i] = ld_image_u32(ce.right ? Rf : Lf, y0 - R + 8 * ce.q + i, (ce.right ? nxr : nxl) + ce.dx, W, H,
                                a.pitch);
         }
         stage_pack(pw, ce.right ? rsm : lsm, ce.col, ce.q);

@@ -65,6 +65,22 @@ __device__ __forceinline__ int xcd_tile(int b, int nb) {
     const int x = b % kNumXcd, i = b / kNumXcd;
     return x < rem ? x * (per + 1) + i : rem * (per + 1) + (x - rem) * per + i;
 }
+// 4 image bytes of row y from column x (little-endian), bytes outside the image read as 0.
+// Interior dwords are one (possibly unaligned) global_load_dword; border dwords go byte-wise.
+__device__ __forceinline__ uint32_t ld_image_u32(const uint8_t* p, int y, int x, int W, int H, int pitch) {
+    if (y < 0 || y >= H) return 0u;
+    const uint8_t* row = p + (int64_t)y * pitch;
+    if (x >= 0 && x + 3 < W) {
+        uint32_t v;
+        __builtin_memcpy(&v, row + x, 4);
+        return v;
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
+    return v;
+}
 constexpr int kMaxFastRadius = 7;  // u16 packed sums stay < 2^16 up to r = 7 (15*15*255 = 57375)
 
 // Host-side launchers (bm_box.hip, bm_aux.hip).  Which box launcher a pass takes, and the workspace sizes named

@@ -59,22 +59,6 @@ __device__ __forceinline__ int win_count(int x, int r, int n) {
     return hi - lo + 1;
 }
 
-// 4 bytes of row y from column x (little-endian), outside the image = 0
-__device__ __forceinline__ uint32_t ld4(const uint8_t* p, int y, int x, int W, int H, int pitch) {
-    if (y < 0 || y >= H) return 0u;
-    const uint8_t* row = p + (int64_t)y * pitch;
-    if (x >= 0 && x + 3 < W) {
-        uint32_t v;
-        __builtin_memcpy(&v, row + x, 4);
-        return v;
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
-    return v;
-}
-
 // disparities per staged right band: 32 keeps LDS <= 52.3 KB at r = 5 with the bank-spread CS stride
 // (3 workgroups/CU; measured occupancy drops to 2 at 54 KB)
 constexpr int kBandChunk = 32;
@@ -87,19 +71,19 @@ constexpr uint32_t kPLow = kPOne - 1;
 // S2V reads each a/b row once per 16-row strip (52 reads instead of 72; its float sums still restart
 // every 8 rows, so the maps do not change).  Roles rotate with the workgroup index, so the
 // co-resident workgroups of a CU put their S1V waves on different SIMDs.
-#ifndef SM_G_ROLES
-#define SM_G_ROLES 1
-#endif
-constexpr bool kGuidedRoles = SM_G_ROLES != 0;
-
-// SM_G_ACC (round 6, default 1): S1H's window sums of the packed columns without unpacking SIp per column (s1h
-// below): 152 -> 142 VALU per wave and d, 459.9 -> 452.9 us per 1080p guided frame, guided + LR 511.1 -> 505.0,
-// maps bit-identical (profiles/microbench/r06_guided_acc_pk_ab.txt).  0 keeps the unpacking form for A/B.
-// Not kept (same file): S2V's (a, b) running sums as v_pk_add_f32 pairs, 100 -> 50 VALU but 462.1 us (+0.5 %):
-// a packed f32 add costs the SIMD about what the two adds it replaces do.
-#ifndef SM_G_ACC
-#define SM_G_ACC 1
-#endif
+// The left-only kernel runs them at every radius.  The right-view kernel runs them at r = 0, 1, 4, 5, where it
+// keeps 3 waves/SIMD with them (<= 168 VGPRs: the output guide values packed as f16 pairs and one validity
+// register, LEAN below), and at r = 3, whose right view runs 2 waves/SIMD either way (598.4 vs 618.8 us per
+// 1080p frame); not at r = 2 (spills at 3 waves/SIMD) nor at r = 6, 7.  Same box, guided + LR, 1080p D=128
+// 32 frames per call, us per frame: r = 5 549.1 -> 523.0, r = 4 532.7 -> 518.9, r = 1 373.0 -> 368.4; 4K D=192
+// 8 frames, r = 5: 3238 -> 3083; maps bit-identical.  The roles at every radius of the right view, at
+// 2 waves/SIMD, ran 552 -> 650 (round 3).
+template <int R, bool RIGHT>
+constexpr bool kGuidedRoles = !RIGHT || (R <= 5 && R != 2);
+// r >= 6 needs > 168 VGPRs without spilling: 2 waves/SIMD there, 3 elsewhere; with the fused right
+// view r = 3 (7 outputs per S2H thread) spills at 168 and also runs at 2
+template <int R, bool RIGHT>
+constexpr int kGuidedWavesPerEU = (R >= 6 || (RIGHT && R == 3)) ? 2 : 3;
 
 // SM_G_MARK=1 (analysis builds only, tools/isa_stage_mix.py): an assembly comment at each stage's entry and exit,
 // so the per-stage VALU mix can be read from the ISA.  The empty asm statements also act as scheduling
@@ -115,8 +99,8 @@ constexpr bool kGuidedRoles = SM_G_ROLES != 0;
 
 // Taller tiles (round 4: 48 rows on 6 waves, 96 rows on one 12-wave workgroup per CU) cut the halo but
 // lost occupancy and ran 1.9x / 1.3x slower; the variants were removed in round 5
-// (git history: SM_G_TALL / SM_G_TALL_RIGHT before commit "guided: drop the measured tall-tile variants").
-template <int R, bool ROLES = kGuidedRoles>
+// (git history: before commit "guided: drop the measured tall-tile variants").
+template <int R, bool ROLES>
 struct GeoF {
     static constexpr int NT = kT;                            // threads per workgroup
     static constexpr int NWV = NT / 64;                      // waves per workgroup
@@ -125,7 +109,7 @@ struct GeoF {
     static constexpr int AW = TW + 2 * R;
     static constexpr int AH = TH + 2 * R;
     static constexpr int PH = TH + 4 * R;
-    // phase 1 runs S1V on SV waves and S2V on the other NWV - SV (kGuidedRoles), else both on all NWV
+    // phase 1 runs S1V on SV waves and S2V on the other NWV - SV (ROLES), else both on all NWV
     static constexpr int SV = ROLES ? NWV / 2 : NWV;
     static constexpr int RPS = TH / (ROLES ? NWV - SV : NWV);   // output rows per S2V wave
     static constexpr int RPW = (AH + SV - 1) / SV;           // A rows per wave in S1V
@@ -136,25 +120,9 @@ struct GeoF {
     static constexpr int NSEG1 = NT / AH;
     static constexpr int SW1 = (AW + NSEG1 - 1) / NSEG1;
     static constexpr int SW2 = (TW + 7) / 8;                 // S2H outputs per thread
-    static constexpr int CSS0 = (NSEG1 * SW1 + 2 * R) > 64 ? (NSEG1 * SW1 + 2 * R) : 64;
-    // strides kept minimal so that r <= 5 fits 3 workgroups per CU (<= 52 KB): an odd CS stride
-    // spreads the S1H rows over the banks (padding mm / a/b rows for banks measured slower).
-    // S2H threads whose last outputs fall past TW read beyond their mm row (the next row, or abp
-    // after the last one) into values that only reach those discarded outputs.  S1H writes every
-    // one of its NSEG1*SW1 columns (those past AW are never read), so a/b rows are that wide.
-    // S1H thread tid reads CS dword h1i*CSS + h1s*SW1 + k (h1i = tid / NSEG1, h1s = tid % NSEG1):
-    // with SW1 odd and CSS == NSEG1*SW1 (mod 32) that is SW1*tid + k (mod 32), a distinct bank for
-    // each lane of a 32-lane group (the odd CS stride left 2-way conflicts, 25 % of LDS cycles)
-    static constexpr int CSS_B = CSS0 + ((NSEG1 * SW1 - CSS0) % 32 + 32) % 32;
-    static constexpr int CSS_OLD = CSS0 + 1;
-    static constexpr int MSA_ = AW % 4 == 2 ? AW : AW + ((6 - AW % 4) % 4);
-    static constexpr int lds_for(int css) {
-        return ((((AHP * css * 4 > PHP * 64 ? AHP * css * 4 : PHP * 64) + 15) & ~15)) + 2 * TH * MSA_ * 4 +
-               AH * (NSEG1 * SW1 > AW ? NSEG1 * SW1 : AW) * 8 + ((PHP * (64 + kBandChunk) + 15) & ~15);
-    }
-    static constexpr int CSS =
-        (SW1 % 2 == 1 && lds_for(CSS_B) <= (R >= 6 ? 81920 : 53248)) ? CSS_B
-                                                                                                       : CSS_OLD;
+    // what bm_guided_plan.h sizes the right-key partials and the reduce by
+    static_assert(TW == guided_tile_w(R) && TH == kGuidedTileH && SW2 == guided_seg_w(R),
+                  "guided_right_partial_bytes follows this geometry");
     // mm is two float planes (sum a, sum b), rows of MSA floats.  S2V stores them lane-consecutively
     // (ds_write_addtid_b32, 2 LDS cycles per 64 lanes against 6 for a float2 ds_write_b64); S2H reads
     // its segment as ds_read_b64 pairs.  MSA = 2 (mod 4): the b64 reads of 32 lanes (32 rows, one
@@ -163,12 +131,30 @@ struct GeoF {
     static constexpr int MSA = AW % 4 == 2 ? AW : AW + ((6 - AW % 4) % 4);
     static constexpr int ABS = NSEG1 * SW1 > AW ? NSEG1 * SW1 : AW;   // float2 per a/b row
     static constexpr int RBW = 64 + kBandChunk;              // right band bytes per P row (one d-chunk)
-    static constexpr int CS_BYTES = ((AHP * CSS * 4 > PHP * 64 ? AHP * CSS * 4 : PHP * 64) + 15) & ~15;  // lt aliases cs
+    // the LDS blocks, in this order: cs (lt aliases it), mm, a/b, right band; only cs depends on the CS stride
+    static constexpr int cs_bytes(int css) {
+        return ((AHP * css * 4 > PHP * 64 ? AHP * css * 4 : PHP * 64) + 15) & ~15;
+    }
     static constexpr int MM_PLANE = TH * MSA * 4;            // bytes per mm plane
     static constexpr int MM_BYTES = 2 * MM_PLANE;
     static constexpr int AB_BYTES = AH * ABS * 8;
     static constexpr int RB_BYTES = (PHP * RBW + 15) & ~15;
-    static constexpr int LDS = CS_BYTES + MM_BYTES + AB_BYTES + RB_BYTES;
+    static constexpr int lds_bytes(int css) { return cs_bytes(css) + MM_BYTES + AB_BYTES + RB_BYTES; }
+    // strides kept minimal so that r <= 5 fits 3 workgroups per CU (<= 52 KB): an odd CS stride
+    // spreads the S1H rows over the banks (padding mm / a/b rows for banks measured slower).
+    // S2H threads whose last outputs fall past TW read beyond their mm row (the next row, or abp
+    // after the last one) into values that only reach those discarded outputs.  S1H writes every
+    // one of its NSEG1*SW1 columns (those past AW are never read), so a/b rows are that wide.
+    // S1H thread tid reads CS dword h1i*CSS + h1s*SW1 + k (h1i = tid / NSEG1, h1s = tid % NSEG1):
+    // with SW1 odd and CSS == NSEG1*SW1 (mod 32) that is SW1*tid + k (mod 32), a distinct bank for
+    // each lane of a 32-lane group (the odd CS stride left 2-way conflicts, 25 % of LDS cycles).
+    // That stride (CSS_B) where SW1 is odd and the workgroups per CU stay, else the odd one
+    static constexpr int CSS0 = (NSEG1 * SW1 + 2 * R) > 64 ? (NSEG1 * SW1 + 2 * R) : 64;
+    static constexpr int CSS_B = CSS0 + ((NSEG1 * SW1 - CSS0) % 32 + 32) % 32;
+    static constexpr int CSS_ODD = CSS0 + 1;
+    static constexpr int CSS = (SW1 % 2 == 1 && lds_bytes(CSS_B) <= (R >= 6 ? 81920 : 53248)) ? CSS_B : CSS_ODD;
+    static constexpr int CS_BYTES = cs_bytes(CSS);
+    static constexpr int LDS = lds_bytes(CSS);
 };
 
 typedef float vf2 __attribute__((ext_vector_type(2)));   // a VGPR pair for asm operands
@@ -291,24 +277,6 @@ __device__ __forceinline__ void s2h_load(uint32_t addr, float (&va)[2 * N], floa
     }
 }
 
-// r >= 6 needs > 168 VGPRs without spilling: 2 waves/SIMD there, 3 elsewhere; with the fused right
-// view r = 3 (7 outputs per S2H thread) spills at 168 and also runs at 2
-// SM_G_ROLES_RIGHT: the phase-1 wave roles in the right-view kernel too.  2 (default): at r = 0, 1, 4, 5,
-// where the kernel keeps 3 waves/SIMD with them (<= 168 VGPRs: the output guide values packed as f16
-// pairs and one validity register, LEAN below), and at r = 3, whose right view runs 2 waves/SIMD either
-// way (598.4 vs 618.8 us per 1080p frame); not at r = 2 (spills at 3 waves/SIMD); 1 (A/B only): every
-// radius, at 2 waves/SIMD; 0: never.
-// Same box, guided + LR, 1080p D=128 32 frames per call, us per frame: r = 5 549.1 -> 523.0, r = 4
-// 532.7 -> 518.9, r = 1 373.0 -> 368.4; 4K D=192 8 frames, r = 5: 3238 -> 3083; maps bit-identical.
-// 1 ran 552 -> 650 (round 3, 2 waves/SIMD)
-#ifndef SM_G_ROLES_RIGHT
-#define SM_G_ROLES_RIGHT 2
-#endif
-template <int R>
-constexpr bool kRolesRight = SM_G_ROLES_RIGHT == 1 || (SM_G_ROLES_RIGHT == 2 && R <= 5 && R != 2);
-template <int R, bool RIGHT>
-constexpr int kGuidedWavesPerEU = (R >= 6 || (RIGHT && (R == 3 || SM_G_ROLES_RIGHT == 1))) ? 2 : 3;
-
 static_assert(GeoF<5, true>::LDS <= 53248 && GeoF<5, false>::LDS <= 53248, "r = 5: three workgroups per CU");
 
 // right-key scale: q * 2^14 in a signed 24-bit field above the 8-bit position field
@@ -322,14 +290,18 @@ constexpr float kRightMin = -8388608.0f;   // -2^23
 // v_min_f32 + v_max_f32 + multiply + convert + v_lshl_or_b32: 527.8 -> 515.4 us per 1080p frame).
 constexpr float kRightScaleSat = 4194304.0f;   // 2^22
 
+// What a pass's left view is (the kernel's `mode`): its validity rule, WTA seed and output
+constexpr int kModeLeft = 0;        // valid d <= W - x, threshold 50 (Device.cu:37, :44); the map into disp
+constexpr int kModeMirrored = 1;    // valid d <= x, no threshold: unreachable since the right view was fused
+constexpr int kModeSliceKeys = 2;   // valid d <= W - x, no threshold; the slice's keys into keys
+
+// The pass over d in [d_lo, d_hi); K: the right-key chain's steps (RIGHT)
 template <int R, bool RIGHT>
 __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fused_kernel(
     const uint8_t* __restrict__ Limg, const uint8_t* __restrict__ Rimg, int W, int H, int pitch, int64_t fstride,
-    int d_lo, int D, float eps, int valid_mode, uint8_t* __restrict__ disp, int out_pitch, int64_t ostride,
+    int d_lo, int d_hi, float eps, int mode, uint8_t* __restrict__ disp, int out_pitch, int64_t ostride,
     int tiles_x, int tiles, int* __restrict__ gpart, int K, int* __restrict__ keys) {
-    // wave roles with the fused right view only where its key chain leaves registers for the taller
-    // strips (kRolesRight: r = 0, 1, 4, 5 at 3 waves/SIMD with the LEAN state below, r = 3 at 2)
-    constexpr bool ROLES = kGuidedRoles && (!RIGHT || kRolesRight<R>);
+    constexpr bool ROLES = kGuidedRoles<R, RIGHT>;
     // the right view with the roles needs S2H's per-output state in fewer registers: I as f16 pairs read
     // by v_fma_mix_f32 (the same single-rounding fma, so the same maps; issued as VOP3P it costs more than
     // the v_fmac the f32 form gets: +0.8 % on the left-only kernel, which keeps that form; at r = 2 the
@@ -362,13 +334,14 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
         const int rbase = px0 - kBandChunk * k - kBandChunk;
         for (int e = tid; e < G::PHP * (G::RBW / 4); e += NT) {
             const int i = e / (G::RBW / 4), j = e - (e / (G::RBW / 4)) * (G::RBW / 4);
-            *reinterpret_cast<uint32_t*>(rb + i * G::RBW + 4 * j) = ld4(Rf, py0 + i, rbase + 4 * j, W, H, pitch);
+            *reinterpret_cast<uint32_t*>(rb + i * G::RBW + 4 * j) =
+                ld_image_u32(Rf, py0 + i, rbase + 4 * j, W, H, pitch);
         }
     };
     stage_band(d_lo / kBandChunk);
     for (int e = tid; e < G::PHP * 16; e += NT) {
         const int i = e >> 4, j = e & 15;
-        *reinterpret_cast<uint32_t*>(lt + i * 64 + 4 * j) = ld4(L, py0 + i, px0 + 4 * j, W, H, pitch);
+        *reinterpret_cast<uint32_t*>(lt + i * 64 + 4 * j) = ld_image_u32(L, py0 + i, px0 + 4 * j, W, H, pitch);
     }
     __syncthreads();
     // phase-1 role of this wave: S1V strip `role` (role < SV) or S2V strip role - SV
@@ -442,8 +415,8 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     int bdd[G::SW2], dlim[LEAN ? 1 : G::SW2];
     // LEAN: the validity d <= W - x (Device.cu:44; mirrored pass: d <= x) as d - dsgn * o <= dl0 for
     // output o, one VGPR instead of one per output (the left-hand side is wave-uniform)
-    const int dsgn = valid_mode != 1 ? -1 : 1;
-    const int dl0 = valid_mode != 1 ? W - (x0 + h2s * G::SW2) : x0 + h2s * G::SW2;
+    const int dsgn = mode != kModeMirrored ? -1 : 1;
+    const int dl0 = mode != kModeMirrored ? W - (x0 + h2s * G::SW2) : x0 + h2s * G::SW2;
     // fused right view: 2^14 / N per output (NaN for outputs outside the image or the tile, whose
     // keys then clamp to the maximum), and the key slots
     float rinv[RIGHT ? G::SW2 : 1];
@@ -458,9 +431,10 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
             oIh[o / 2] = (o % 2 == 0) ? ih : (oIh[o / 2] | (ih << 16));
         } else {
             oI[o] = iv;
-            dlim[o] = valid_mode != 1 ? (W - x) : x;   // d <= W - x (Device.cu:44); mirrored pass: d <= x
+            dlim[o] = mode != kModeMirrored ? (W - x) : x;   // d <= W - x (Device.cu:44); mirrored pass: d <= x
         }
-        bq[o] = valid_mode == 0 ? 50.0f * (float)(win_count(x, R, W) * win_count(oy, R, H)) : __builtin_huge_valf();
+        bq[o] = mode == kModeLeft ? 50.0f * (float)(win_count(x, R, W) * win_count(oy, R, H))
+                                  : __builtin_huge_valf();
         bdd[o] = -256;
         if constexpr (RIGHT) {
             rinv[o] = ok ? kRightScaleSat / (float)(win_count(x, R, W) * win_count(oy, R, H))
@@ -558,35 +532,24 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
         uint32_t v[G::SW1 + 2 * R];
 #pragma unroll
         for (int k = 0; k < G::SW1 + 2 * R; ++k) v[k] = row[k];
-#if SM_G_ACC
-        // SM_G_ACC: the packed column sums are summed as they are (acc, wrapping u32) beside the exact Sp; the
-        // window's SIp < 2^24 is then acc - Sp * 2^20 (mod 2^32, exact), one v_mad_i32_i24 per output instead of
-        // an and + add per column
+        // the packed column sums are summed as they are (acc, wrapping u32) beside the exact Sp; the window's
+        // SIp < 2^24 is then acc - Sp * 2^20 (mod 2^32, exact), one v_mad_i32_i24 per output instead of an and + add
+        // per column (round 6: 152 -> 142 VALU per wave and d, 459.9 -> 452.9 us per 1080p guided frame, guided + LR
+        // 511.1 -> 505.0, maps bit-identical; profiles/microbench/r06_guided_acc_pk_ab.txt.  Not kept, same file:
+        // S2V's (a, b) running sums as v_pk_add_f32 pairs, 100 -> 50 VALU but 462.1 us (+0.5 %): a packed f32 add
+        // costs the SIMD about what the two adds it replaces do)
         uint32_t sp = 0, acc = 0;
 #pragma unroll
         for (int k = 0; k < 2 * R; ++k) {
             sp += v[k] >> 20;
             acc += v[k];
         }
-#else
-        uint32_t sp = 0, sip = 0;
-#pragma unroll
-        for (int k = 0; k < 2 * R; ++k) {
-            sp += v[k] >> 20;
-            sip += v[k] & k_plow;
-        }
-#endif
 #pragma unroll
         for (int o = 0; o < G::SW1; ++o) {
-#if SM_G_ACC
             sp += v[o + 2 * R] >> 20;
             acc += v[o + 2 * R];
             uint32_t sip;
             asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(sip) : "v"(sp), "s"(k_m2p20), "v"(acc));
-#else
-            sp += v[o + 2 * R] >> 20;
-            sip += v[o + 2 * R] & k_plow;
-#endif
             // N*SIp - SI*Sp = N^2 cov(I, p), |.| < 2^30, exactly (mod 2^32), from 24-bit products (written out:
             // the compiler otherwise turns one product into a quarter-rate v_mul_lo_u32).  -SI and Sp fit
             // signed 24-bit operands at every radius.  SIp <= (2R+1)^2 * 255^2 does up to r = 5 (121 * 255^2
@@ -611,11 +574,7 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
                          : "v"(h1off), "v"(__builtin_bit_cast(double, make_float2(a, b))), "i"(8 * o)
                          : "memory");
             sp -= v[o] >> 20;
-#if SM_G_ACC
             acc -= v[o];
-#else
-            sip -= v[o] & k_plow;
-#endif
         }
         G_MARK("end");
     };
@@ -741,24 +700,23 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     if (is_s1v) s1v(0, std::true_type{}, std::false_type{});
     // (round 5: stopping the left-only kernel at the tile's last valid d, W - x0, measured +0.7 % slower on the
     // 1080p guided launch (453.5 -> 456.9 us per frame, profiles/microbench/r05_skip_invalid_pairs_ab.txt): not kept)
-    const int Dk = D;
-    const bool s1_nomask = px0 >= Dk - 1 && px0 >= 0 && px0 + 63 < W;
-    const bool s2_lim = valid_mode != 1 ? (Dk - 1 > W - (x0 + G::TW - 1)) : (Dk - 1 > x0);
+    const bool s1_nomask = px0 >= d_hi - 1 && px0 >= 0 && px0 + 63 < W;
+    const bool s2_lim = mode != kModeMirrored ? (d_hi - 1 > W - (x0 + G::TW - 1)) : (d_hi - 1 > x0);
     lds_barrier();
     s1h_stats();
     __syncthreads();
     // buffers: cs (S1V -> S1H), abp (S1H -> S2V), mm (S2V -> S2H); each producer of iteration d+1
     // runs after the barrier that ends the consumer of iteration d.  The right band (read only by
     // S1V) is restaged for the next d-chunk in the second phase of the chunk's last iteration.
-    for (int d = d_lo; d <= Dk; ++d) {
-        if (is_s1v && d < Dk) {
+    for (int d = d_lo; d <= d_hi; ++d) {
+        if (is_s1v && d < d_hi) {
             if (s1_nomask) s1v(d, std::false_type{}, std::true_type{});
             else s1v(d, std::false_type{}, std::false_type{});
         }
         if ((!ROLES || !is_s1v) && d > d_lo) s2v();
         lds_barrier();
-        if (d + 1 < Dk && ((d + 1) & (kBandChunk - 1)) == 0) stage_band((d + 1) / kBandChunk);
-        if (d < Dk) s1h();
+        if (d + 1 < d_hi && ((d + 1) & (kBandChunk - 1)) == 0) stage_band((d + 1) / kBandChunk);
+        if (d < d_hi) s1h();
         if (d > d_lo) {
             if (s2_lim) s2h(d - 1, std::true_type{});
             else s2h(d - 1, std::false_type{});
@@ -767,9 +725,9 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     }
     // drain the right-key chain: 8 SW2 - 1 more steps move every slot out through the last segment
     if constexpr (RIGHT) {
-        for (int k = D; k < d_lo + K; ++k) chain_step(k);
+        for (int k = d_hi; k < d_lo + K; ++k) chain_step(k);
     }
-    if (valid_mode == 2) {
+    if (mode == kModeSliceKeys) {
         // d-slice keys: (q * 2^14 << 8) | d, INT_MAX where no d of the slice is valid
         int* Kf = keys + (int64_t)frame * H * W;
 #pragma unroll
@@ -866,150 +824,64 @@ __global__ __launch_bounds__(256) void guided_right_reduce_kernel(const int* __r
     }
 }
 
-// the reduce with the smallest instantiated MAXT >= (K + TW - 1) / TW + 1 (D <= 256, TW >= 36: <= 10)
-template <int TH>
-hipError_t launch_right_reduce(const int* gpart, int tiles_x, int tiles_y, int batch, int TW, int span, int K, int W,
-                               int H, uint8_t* right, int rpitch, int64_t rstride, int* rkeys, int d_lo,
-                               hipStream_t s) {
-    const int need = (K + TW - 1) / TW + 1;
-    const dim3 grid((unsigned)((W + 63) / 64), (unsigned)tiles_y, (unsigned)batch);
-    const int tiles = tiles_x * tiles_y;
-#define SM_RIGHT_REDUCE(M)                                                                                      \
-    hipLaunchKernelGGL((guided_right_reduce_kernel<TH, M>), grid, dim3(256), 0, s, gpart, tiles_x, tiles, TW, span, K, \
-                       W, H, right, rpitch, rstride, rkeys, d_lo)
-    if (need <= 4) SM_RIGHT_REDUCE(4);
-    else if (need <= 6) SM_RIGHT_REDUCE(6);
-    else if (need <= 8) SM_RIGHT_REDUCE(8);
-    else if (need <= 10) SM_RIGHT_REDUCE(10);
+// the reduce with the smallest instantiated MAXT >= the tiles covering one right pixel (guided_reduce_tiles: <= 10)
+template <int R>
+hipError_t launch_right_reduce(const GuidedPass& p, int tiles_x, int tiles_y, hipStream_t s) {
+    constexpr int TW = guided_tile_w(R), TH = kGuidedTileH;
+    const int D = p.d_hi - p.d_lo;
+    const int need = guided_reduce_tiles(R, D);
+    const dim3 grid((unsigned)((p.W + 63) / 64), (unsigned)tiles_y, (unsigned)p.batch);
+    auto run = [&](auto maxt) {
+        hipLaunchKernelGGL((guided_right_reduce_kernel<TH, decltype(maxt)::value>), grid, dim3(256), 0, s, p.gpart,
+                           tiles_x, tiles_x * tiles_y, TW, guided_chain_span(R), guided_chain_len(R, D), p.W, p.H,
+                           p.right_map, p.rpitch, p.rstride, p.right_keys, p.d_lo);
+    };
+    if (need <= 4) run(std::integral_constant<int, 4>{});
+    else if (need <= 6) run(std::integral_constant<int, 6>{});
+    else if (need <= 8) run(std::integral_constant<int, 8>{});
+    else if (need <= kMaxGuidedReduceTiles) run(std::integral_constant<int, kMaxGuidedReduceTiles>{});
     else return hipErrorInvalidValue;
-#undef SM_RIGHT_REDUCE
     return hipGetLastError();
 }
 
+// A validated pass (launch_guided) at radius R: the left-only kernel, or with p.gpart the right-view kernel and
+// the reduce over its partials (a slice's chains are laid out for d - d_lo)
 template <int R>
-hipError_t run_fused(const uint8_t* L, const uint8_t* Rimg, int W, int H, int pitch, int64_t fstride, int batch,
-                     int d_lo, int D, float eps, int valid_mode, uint8_t* disp, int out_pitch, int64_t ostride,
-                     int* gpart, uint8_t* right, int rpitch, int64_t rstride, int* keys, hipStream_t s,
-                     int* rkeys = nullptr) {
-    using G = GeoF<R, false>;   // tile geometry (TW, TH, SW2) is the same with or without the roles
-    const int tiles_x = (W + G::TW - 1) / G::TW, tiles_y = (H + G::TH - 1) / G::TH;
-    const int64_t blocks = (int64_t)tiles_x * tiles_y * batch;
+hipError_t run_fused(const GuidedPass& p, hipStream_t s) {
+    constexpr int TW = guided_tile_w(R), TH = kGuidedTileH;
+    const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH;
+    const int64_t blocks = (int64_t)tiles_x * tiles_y * p.batch;
     if (blocks <= 0 || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    // the left-only kernel may run the phase-1 wave roles: its LDS plan is GeoF<R, kGuidedRoles>'s
-    constexpr size_t lds_left = (size_t)GeoF<R, kGuidedRoles>::LDS;
-    constexpr size_t lds_right = (size_t)GeoF<R, kGuidedRoles && kRolesRight<R>>::LDS;
-    if (!gpart) {
-        hipLaunchKernelGGL((guided_fused_kernel<R, false>), dim3((unsigned)blocks), dim3(kT), lds_left, s, L,
-                           Rimg, W, H, pitch, fstride, d_lo, D, eps, valid_mode, disp, out_pitch, ostride, tiles_x,
-                           tiles_x * tiles_y, nullptr, 0, keys);
+    const int mode = p.keys ? kModeSliceKeys : kModeLeft;
+    constexpr size_t lds_left = GeoF<R, kGuidedRoles<R, false>>::LDS, lds_right = GeoF<R, kGuidedRoles<R, true>>::LDS;
+    if (!p.gpart) {
+        hipLaunchKernelGGL((guided_fused_kernel<R, false>), dim3((unsigned)blocks), dim3(kT), lds_left, s, p.left,
+                           p.right, p.W, p.H, p.pitch, p.frame_stride, p.d_lo, p.d_hi, p.eps, mode, p.disp, p.out_pitch,
+                           p.out_frame_stride, tiles_x, tiles_x * tiles_y, nullptr, 0, p.keys);
         return hipGetLastError();
     }
-    // with the right view: valid_mode 0 (d_lo 0, the left map + dR) or 2 (a d slice: left keys + right keys in
-    // rkeys, the chains laid out for d - d_lo)
-    const int span = 8 * G::SW2;
-    const int K = (D - d_lo) + span - 1;
-    hipLaunchKernelGGL((guided_fused_kernel<R, true>), dim3((unsigned)blocks), dim3(kT), lds_right, s, L, Rimg,
-                       W, H, pitch, fstride, d_lo, D, eps, valid_mode, disp, out_pitch, ostride, tiles_x,
-                       tiles_x * tiles_y, gpart, K, keys);
-    hipError_t e = hipGetLastError();
+    hipLaunchKernelGGL((guided_fused_kernel<R, true>), dim3((unsigned)blocks), dim3(kT), lds_right, s, p.left,
+                       p.right, p.W, p.H, p.pitch, p.frame_stride, p.d_lo, p.d_hi, p.eps, mode, p.disp, p.out_pitch,
+                       p.out_frame_stride, tiles_x, tiles_x * tiles_y, p.gpart, guided_chain_len(R, p.d_hi - p.d_lo),
+                       p.keys);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_right_reduce<G::TH>(gpart, tiles_x, tiles_y, batch, G::TW, span, K, W, H, right, rpitch, rstride,
-                                      rkeys, d_lo, s);
-}
-
-template <int R>
-size_t partial_bytes(int W, int H, int D, int batch) {   // D: the pass's span d_hi - d_lo
-    using G = GeoF<R, false>;
-    const int64_t tiles = (int64_t)((W + G::TW - 1) / G::TW) * ((H + G::TH - 1) / G::TH);
-    return (size_t)(tiles * batch * (D + 8 * G::SW2 - 1) * G::TH * 4);
+    return launch_right_reduce<R>(p, tiles_x, tiles_y, s);
 }
 
 }  // namespace
 
-hipError_t launch_guided_match(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-                               int64_t frame_stride, int radius, int D, float eps, int valid_mode, uint8_t* disp,
-                               int out_pitch, int64_t out_frame_stride, hipStream_t s) {
-    return launch_guided_match_lr(L, R, W, H, pitch, batch, frame_stride, radius, D, eps, valid_mode, disp, out_pitch,
-                                  out_frame_stride, nullptr, nullptr, 0, 0, s);
-}
+static_assert(kMaxGuidedRadius == kMaxFastRadius && kMaxGuidedDisp == kMaxDisp, "the plan's limits are the library's");
 
-size_t guided_right_partial_bytes(int W, int H, int radius, int D, int batch) {
-#define SM_GUIDED_BYTES(r) \
-    case r: return partial_bytes<r>(W, H, D, batch)
-    switch (radius) {
-        SM_GUIDED_BYTES(0);
-        SM_GUIDED_BYTES(1);
-        SM_GUIDED_BYTES(2);
-        SM_GUIDED_BYTES(3);
-        SM_GUIDED_BYTES(4);
-        SM_GUIDED_BYTES(5);
-        SM_GUIDED_BYTES(6);
-        SM_GUIDED_BYTES(7);
-        default: return 0;
-    }
-#undef SM_GUIDED_BYTES
-}
-
-hipError_t launch_guided_match_lr(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-                                  int64_t frame_stride, int radius, int D, float eps, int valid_mode, uint8_t* disp,
-                                  int out_pitch, int64_t out_frame_stride, int* gpart, uint8_t* right, int rpitch,
-                                  int64_t rstride, hipStream_t s) {
-    if (D < 1 || D > kMaxDisp) return hipErrorInvalidValue;
-    if (gpart && (!right || valid_mode != 0)) return hipErrorInvalidValue;
-#define SM_GUIDED_CASE(r) \
-    case r: return run_fused<r>(L, R, W, H, pitch, frame_stride, batch, 0, D, eps, valid_mode, disp, out_pitch, out_frame_stride, gpart, right, rpitch, rstride, nullptr, s)
-    switch (radius) {
-        SM_GUIDED_CASE(0);
-        SM_GUIDED_CASE(1);
-        SM_GUIDED_CASE(2);
-        SM_GUIDED_CASE(3);
-        SM_GUIDED_CASE(4);
-        SM_GUIDED_CASE(5);
-        SM_GUIDED_CASE(6);
-        SM_GUIDED_CASE(7);
-        default: return hipErrorInvalidValue;
-    }
-#undef SM_GUIDED_CASE
-}
-
-hipError_t launch_guided_slice_keys(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-                                    int64_t frame_stride, int radius, int d_lo, int d_hi, float eps, int* keys,
-                                    hipStream_t s) {
-    if (d_lo < 0 || d_hi <= d_lo || d_hi > kMaxDisp || !keys) return hipErrorInvalidValue;
-#define SM_GUIDED_SLICE(r) \
-    case r: return run_fused<r>(L, R, W, H, pitch, frame_stride, batch, d_lo, d_hi, eps, 2, nullptr, 0, 0, nullptr, nullptr, 0, 0, keys, s)
-    switch (radius) {
-        SM_GUIDED_SLICE(0);
-        SM_GUIDED_SLICE(1);
-        SM_GUIDED_SLICE(2);
-        SM_GUIDED_SLICE(3);
-        SM_GUIDED_SLICE(4);
-        SM_GUIDED_SLICE(5);
-        SM_GUIDED_SLICE(6);
-        SM_GUIDED_SLICE(7);
-        default: return hipErrorInvalidValue;
-    }
-#undef SM_GUIDED_SLICE
-}
-
-hipError_t launch_guided_slice_lr_keys(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-                                       int64_t frame_stride, int radius, int d_lo, int d_hi, float eps, int* keys,
-                                       int* right_keys, int* gpart, hipStream_t s) {
-    if (d_lo < 0 || d_hi <= d_lo || d_hi > kMaxDisp || !keys || !right_keys || !gpart) return hipErrorInvalidValue;
-#define SM_GUIDED_SLICE_LR(r) \
-    case r: return run_fused<r>(L, R, W, H, pitch, frame_stride, batch, d_lo, d_hi, eps, 2, nullptr, 0, 0, gpart, nullptr, 0, 0, keys, s, right_keys)
-    switch (radius) {
-        SM_GUIDED_SLICE_LR(0);
-        SM_GUIDED_SLICE_LR(1);
-        SM_GUIDED_SLICE_LR(2);
-        SM_GUIDED_SLICE_LR(3);
-        SM_GUIDED_SLICE_LR(4);
-        SM_GUIDED_SLICE_LR(5);
-        SM_GUIDED_SLICE_LR(6);
-        SM_GUIDED_SLICE_LR(7);
-        default: return hipErrorInvalidValue;
-    }
-#undef SM_GUIDED_SLICE_LR
+hipError_t launch_guided(const GuidedPass& p, hipStream_t s) {
+    if (!guided_pass_ok(p.W, p.H, p.radius, p.d_lo, p.d_hi, p.batch)) return hipErrorInvalidValue;
+    if ((p.disp != nullptr) == (p.keys != nullptr)) return hipErrorInvalidValue;
+    if (p.disp && p.d_lo != 0) return hipErrorInvalidValue;
+    // the right view: gpart and the output that goes with the left one, or none of the three
+    if (p.disp ? p.right_keys != nullptr : p.right_map != nullptr) return hipErrorInvalidValue;
+    if ((p.gpart != nullptr) != (p.right_map != nullptr || p.right_keys != nullptr)) return hipErrorInvalidValue;
+    return with_radius<0, kMaxFastRadius>(p.radius, hipErrorInvalidValue,
+                                          [&](auto r) { return run_fused<decltype(r)::value>(p, s); });
 }
 
 hipError_t launch_guided_keys_to_disp(const int* keys, int W, int H, uint8_t* disp, int out_pitch, hipStream_t s) {

@@ -244,7 +244,6 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         if (rc) return rc;
     }
     const bool volume = sgm || census;   // both maps come out of one cost volume (run_volume)
-    const bool guided_right = lr && guided;   // right view fused into the guided pass (bm_guided.hip)
     if ((flags & SM_DEVICE_CU_GRID) != 0) {   // Device.cu's launch geometry, frame by frame (bm_literal.hip)
         if (flags != SM_DEVICE_CU_GRID || lr)
             return fail(SM_ERR_INVALID_ARG, "SM_DEVICE_CU_GRID is box aggregation only (flags 0x%x)", flags);
@@ -267,6 +266,10 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         return run_staged(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, med, disp, opitch, ostride);
     }
 
+    if (guided) {
+        const int rc = guided_radius_check(radius);
+        if (rc) return rc;
+    }
     const bool box = !guided && !volume;
     sm::BoxPlan plan{};
     if (box)
@@ -309,15 +312,29 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
         const VolumeOut o{lmap, lpitch, lstride, lr ? right_map : nullptr};
         int rc = run_volume(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, sgm, census, sgm_p1, sgm_p2, o);
         if (rc) return rc;
-    } else if (guided_right) {
-        int* rpart = nullptr;
-        int rc = ws.get(h->rpart, sm::guided_right_partial_bytes(W, H, radius, D, batch), &rpart);
-        if (rc) return rc;
-        SM_HIP(sm::launch_guided_match_lr(L, R, W, H, pitch, batch, fstride, radius, D, h->guided_eps, 0, lmap, lpitch,
-                                         lstride, rpart, right_map, W, P, s));
     } else if (guided) {
-        SM_HIP(sm::launch_guided_match(L, R, W, H, pitch, batch, fstride, radius, D, h->guided_eps, 0, lmap, lpitch,
-                                      lstride, s));
+        sm::GuidedPass g{};   // d_lo 0, no keys
+        g.left = L;
+        g.right = R;
+        g.W = W;
+        g.H = H;
+        g.pitch = pitch;
+        g.frame_stride = fstride;
+        g.batch = batch;
+        g.radius = radius;
+        g.d_hi = D;
+        g.eps = h->guided_eps;
+        g.disp = lmap;
+        g.out_pitch = lpitch;
+        g.out_frame_stride = lstride;
+        if (lr) {   // the right view fused into the same pass (right keys from the left costs)
+            int rc = ws.get(h->rpart, sm::guided_right_partial_bytes(W, H, radius, D, batch), &g.gpart);
+            if (rc) return rc;
+            g.right_map = right_map;
+            g.rpitch = W;
+            g.rstride = P;
+        }
+        SM_HIP(sm::launch_guided(g, s));
     } else {
         BoxRightOut ro;
         // without the median the tile kernels match, form the right view and check in one pass over the partials

@@ -14,6 +14,25 @@ uint32_t dslice_none_key(int radius, bool guided) { return guided ? 0x7FFFFFFFu 
 // both aggregations, since box right keys are sign-flipped (kRightKeyFlip) and every right-key MIN is signed
 constexpr uint32_t kNoRightKey = 0x7FFFFFFFu;
 
+// One frame's guided slice pass into `keys`, left view only
+sm::GuidedPass guided_slice_pass(const sm_handle* h, const uint8_t* dL, const uint8_t* dR, int W, int H, int pitch,
+                                 int64_t fstride, int radius, int d_lo, int d_hi, int* keys) {
+    sm::GuidedPass g{};
+    g.left = dL;
+    g.right = dR;
+    g.W = W;
+    g.H = H;
+    g.pitch = pitch;
+    g.frame_stride = fstride;
+    g.batch = 1;
+    g.radius = radius;
+    g.d_lo = d_lo;
+    g.d_hi = d_hi;
+    g.eps = h->guided_eps;
+    g.keys = keys;
+    return g;
+}
+
 // The slice pass over [d_lo, d_hi) of frames already on the device (pitch `pitch`): left keys, and with
 // `rkeys` the right view's keys from the same fused pass (its per-tile partials in the handle's rpart
 // workspace).  Keys are [H][W]; no padding.  The box kernels and their workspaces are plan_box_pass's
@@ -23,16 +42,14 @@ int slice_keys_pass(WsScope& ws, sm_handle* h, const uint8_t* dL, const uint8_t*
     hipStream_t s = ws.stream();
     const int64_t P = (int64_t)W * H;
     if (guided) {
-        if (!rkeys) {
-            SM_HIP(sm::launch_guided_slice_keys(dL, dR, W, H, pitch, 1, P, radius, d_lo, d_hi, h->guided_eps,
-                                                reinterpret_cast<int*>(keys), s));
-            return SM_OK;
+        sm::GuidedPass g =
+            guided_slice_pass(h, dL, dR, W, H, pitch, P, radius, d_lo, d_hi, reinterpret_cast<int*>(keys));
+        if (rkeys) {
+            int rc = ws.get(h->rpart, sm::guided_right_partial_bytes(W, H, radius, d_hi - d_lo, 1), &g.gpart);
+            if (rc) return rc;
+            g.right_keys = reinterpret_cast<int*>(rkeys);
         }
-        int* rpart = nullptr;
-        int rc = ws.get(h->rpart, sm::guided_right_partial_bytes(W, H, radius, d_hi - d_lo, 1), &rpart);
-        if (rc) return rc;
-        SM_HIP(sm::launch_guided_slice_lr_keys(dL, dR, W, H, pitch, 1, P, radius, d_lo, d_hi, h->guided_eps,
-                                               reinterpret_cast<int*>(keys), reinterpret_cast<int*>(rkeys), rpart, s));
+        SM_HIP(sm::launch_guided(g, s));
         return SM_OK;
     }
     sm::MatchArgs a{};
@@ -85,8 +102,10 @@ int dslice_check(const DsliceCfg& c, unsigned flags) {
     if ((flags & ~(unsigned)(SM_AGG_GUIDED | SM_LR_CHECK)) != 0u)
         return fail(SM_ERR_INVALID_ARG,
                     "d-slice mode: flags 0x%x (box or SM_AGG_GUIDED, optionally SM_LR_CHECK; no median, staged)", flags);
-    if (c.guided && c.radius > sm::kMaxFastRadius)
-        return fail(SM_ERR_INVALID_ARG, "guided aggregation: radius %d > %d", c.radius, sm::kMaxFastRadius);
+    if (c.guided) {
+        const int rc = guided_radius_check(c.radius);
+        if (rc) return rc;
+    }
     if (c.lr && !c.guided &&
         sm::plan_box_pass({c.W, c.H, c.W, c.radius, 0, c.D, 1}, sm::RightWant::Keys).right == sm::BoxRight::Unsupported)
         return fail(SM_ERR_INVALID_ARG, "d-slice LR: box radius %d > %d needs the wide path (width <= %d)", c.radius,
@@ -189,14 +208,15 @@ SM_API int sm_guided_slice_keys_device(sm_handle* h, const uint8_t* d_left, cons
                                        void* stream) {
     int rc = check_geometry(h, width, height, pitch, radius, d_hi > 0 ? d_hi : 1);
     if (rc) return rc;
-    if (radius > sm::kMaxFastRadius)
-        return fail(SM_ERR_INVALID_ARG, "guided aggregation: radius %d > %d", radius, sm::kMaxFastRadius);
+    rc = guided_radius_check(radius);
+    if (rc) return rc;
     rc = slice_check(d_lo, d_hi);
     if (rc) return rc;
     if (!d_left || !d_right || !d_keys) return fail(SM_ERR_INVALID_ARG, "null device pointer");
     SM_HIP(hipSetDevice(h->device));
-    SM_HIP(sm::launch_guided_slice_keys(d_left, d_right, width, height, pitch, 1, (int64_t)pitch * height, radius,
-                                        d_lo, d_hi, h->guided_eps, d_keys, stream_of(stream)));
+    const sm::GuidedPass g =
+        guided_slice_pass(h, d_left, d_right, width, height, pitch, (int64_t)pitch * height, radius, d_lo, d_hi, d_keys);
+    SM_HIP(sm::launch_guided(g, stream_of(stream)));
     return SM_OK;
 }
 

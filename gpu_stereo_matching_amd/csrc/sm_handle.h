@@ -201,6 +201,13 @@ int check_capacity(const sm_handle* h, int width, int height, int num_disp);
 int census_check(int width, int radius, unsigned flags);
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out);
 
+// SM_AGG_GUIDED's radii (bm_guided_plan.h): every guided entry rejects the others before it takes a workspace
+inline int guided_radius_check(int radius) {
+    if (radius > sm::kMaxGuidedRadius)
+        return fail(SM_ERR_INVALID_ARG, "guided aggregation: radius %d > %d", radius, sm::kMaxGuidedRadius);
+    return SM_OK;
+}
+
 inline uint32_t seed_key(int radius) {
     const uint32_t win = 2u * (uint32_t)radius + 1u;
     return (50u * win * win) << 8;  // Device.cu:37 start value, d field 0

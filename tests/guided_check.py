@@ -24,6 +24,30 @@ def tie_aware_check(gpu, q, best, D, W):
     return ok, ok_exact
 
 
+def check_guided_lr(matcher, oracle, L, R, r, D, eps, min_exact=0.99):
+    """Guided + LR with the right view fused into the guided pass: the right map is STMatching's
+    WTA of C_R(y, u, d) = C_L(y, u + d, d) (StereoHelper.cpp:131-180) on the guided left costs.
+    Left and right maps are judged tie-aware against the fp64 oracle (the right keys also carry the
+    2^-14 fixed-point quantisation, far inside TOL); the checked map and mask must equal the
+    reference's LR rule (StereoDisparity.cpp:136-147) applied to the returned maps, bit for bit."""
+    H, W = L.shape
+    disp_o, q, best = oracle.guided_disp(L, R, r, D, eps, want_q=True)
+    left = matcher.match(L, R, r, D, agg="guided")
+    ok, _ = tie_aware_check(left, q, {"disp": disp_o, "best": best}, D, W)
+    assert ok.all(), f"left: {int((~ok).sum())} pixels outside the tie-aware tolerance"
+    chk, rd, mask = matcher.match_lr(L, R, r, D, agg="guided")
+    rd_o, cr, best_r = oracle.right_wta_float(q)
+    ys, us = np.mgrid[0:H, 0:W]
+    assert (rd < D).all()
+    cost_g = cr[rd.astype(np.int64), ys, us]
+    ok_r = (rd == rd_o) | (cost_g <= best_r + TOL)
+    assert ok_r.all(), f"right: {int((~ok_r).sum())} pixels outside the tie-aware tolerance"
+    assert (rd == rd_o).mean() > min_exact
+    chk_o, mask_o = oracle.lr_check(left, rd)
+    assert np.array_equal(chk, chk_o) and np.array_equal(mask, mask_o)
+    return mask
+
+
 def guided_reference(oracle, L, R, r, D, eps):
     """The fp64 oracle's volume and both views' WTA for the tie-aware rules: a dict with the left map
     ("disp"), best left cost ("best"), the q volume ("q"), the right map ("rdisp"), the right cost volume

@@ -10,7 +10,7 @@ reports no match.
 import numpy as np
 import pytest
 
-from guided_check import tie_aware_check
+from guided_check import check_guided_lr, tie_aware_check
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-4 * 255 * 255
@@ -63,37 +63,12 @@ def test_guided_synthetic_ragged(matcher, oracle, W, H, D, r):
     assert ok.all(), f"{int((~ok).sum())} pixels outside the tie-aware tolerance"
 
 
-def _check_guided_lr(matcher, oracle, L, R, r, D, min_exact=0.99):
-    """Guided + LR with the right view fused into the guided pass: the right map is STMatching's
-    WTA of C_R(y, u, d) = C_L(y, u + d, d) (StereoHelper.cpp:131-180) on the guided left costs.
-    Left and right maps are judged tie-aware against the fp64 oracle (the right keys also carry the
-    2^-14 fixed-point quantisation, far inside TOL); the checked map and mask must equal the
-    reference's LR rule (StereoDisparity.cpp:136-147) applied to the returned maps, bit for bit."""
-    from guided_check import TOL
-    H, W = L.shape
-    disp_o, q, best = oracle.guided_disp(L, R, r, D, EPS, want_q=True)
-    left = matcher.match(L, R, r, D, agg="guided")
-    ok, _ = tie_aware_check(left, q, {"disp": disp_o, "best": best}, D, W)
-    assert ok.all(), f"left: {int((~ok).sum())} pixels outside the tie-aware tolerance"
-    chk, rd, mask = matcher.match_lr(L, R, r, D, agg="guided")
-    rd_o, cr, best_r = oracle.right_wta_float(q)
-    ys, us = np.mgrid[0:H, 0:W]
-    assert (rd < D).all()
-    cost_g = cr[rd.astype(np.int64), ys, us]
-    ok_r = (rd == rd_o) | (cost_g <= best_r + TOL)
-    assert ok_r.all(), f"right: {int((~ok_r).sum())} pixels outside the tie-aware tolerance"
-    assert (rd == rd_o).mean() > min_exact
-    chk_o, mask_o = oracle.lr_check(left, rd)
-    assert np.array_equal(chk, chk_o) and np.array_equal(mask, mask_o)
-    return mask
-
-
 @pytest.mark.parametrize("r,D", [(5, 64), (3, 48), (0, 16), (7, 32), (1, 100), (4, 80), (2, 40)])
 def test_guided_lr_art(matcher, oracle, gray, r, D):
-    """Every right-view build: with the phase-1 wave roles (r = 0, 1, 3, 4, 5, kRolesRight) and without
+    """Every right-view build: with the phase-1 wave roles (r = 0, 1, 3, 4, 5, kGuidedRoles) and without
     (r = 2, 7)."""
     L, R = gray["Art_/view1"], gray["Art_/view5"]
-    mask = _check_guided_lr(matcher, oracle, L, R, r, D)
+    mask = check_guided_lr(matcher, oracle, L, R, r, D, EPS)
     assert 0.3 < mask.mean() < 1.0
 
 
@@ -101,7 +76,7 @@ def test_guided_lr_art(matcher, oracle, gray, r, D):
                                      (130, 33, 64, 6)])
 def test_guided_lr_synthetic_ragged(matcher, oracle, W, H, D, r):
     L, R = oracle.synth_pair(W * 3 + H, W, H, max(D, 16))
-    _check_guided_lr(matcher, oracle, L, R, r, D)
+    check_guided_lr(matcher, oracle, L, R, r, D, EPS)
 
 
 def test_guided_lr_flat(matcher, oracle):
@@ -319,4 +294,4 @@ def test_fuzz_guided_and_lr(matcher, oracle, seed):
     ok, _ = tie_aware_check(got, q, {"disp": disp_o, "best": best}, D, W)
     assert ok.all(), f"{int((~ok).sum())} pixels outside the tie-aware tolerance {(W, H, r, D)}"
     # tie-heavy textures: fp32 picks among fp64-equal costs freely, so no exact-match floor here
-    _check_guided_lr(matcher, oracle, L, R, r, D, min_exact=0.0)
+    check_guided_lr(matcher, oracle, L, R, r, D, EPS, min_exact=0.0)

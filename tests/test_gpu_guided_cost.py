@@ -19,7 +19,7 @@ from guided_check import TOL
 
 pytestmark = pytest.mark.gpu
 
-# the fused right-view kernel's build per radius (bm_guided.hip: kRolesRight, LEAN = the wave roles with I as f16
+# the fused right-view kernel's build per radius (bm_guided.hip: kGuidedRoles, LEAN = the wave roles with I as f16
 # pairs read by v_fma_mix_f32; r = 3 runs it at 2 waves/SIMD, r = 2, 6, 7 run without the roles, f32 fma)
 LR_VARIANT = {0: "lean", 1: "lean", 2: "no roles", 3: "lean, 2 waves", 4: "lean", 5: "lean", 6: "no roles",
               7: "no roles"}

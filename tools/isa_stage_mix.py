@@ -4,7 +4,7 @@ instructions and issue cycles (tools/isa_mix.py's measured weights) per instance
 per disparity: one instance of a stage's code is what one wave executes for one d (the stages are fully unrolled).
 
     python tools/isa_stage_mix.py [--json] [R] [RIGHT]    # default R = 5, RIGHT = 0
-    SM_G_FLAGS="-DSM_G_ACC=1" python tools/isa_stage_mix.py   # a variant's mix
+    SM_G_FLAGS="-DNAME=1" python tools/isa_stage_mix.py   # extra compiler flags: an experiment's mix
 """
 import collections
 import json
