@@ -56,7 +56,7 @@ constexpr bool kPairedScatter = (R != 3);
 // not, so phase H keeps the two halves in separate u32 sums; the longer CS rows and the 2r+1-row
 // ring need more than 128 VGPRs (2 waves/SIMD)
 template <int R>
-constexpr bool kWideR = R > 7;
+constexpr bool kWideR = R > kMaxFastRadius;
 template <bool RIGHT, int R>
 constexpr int kMinWavesPerEU = ((RIGHT && !kWideRight<RIGHT, R>) || kWideR<R>) ? 2 : 4;
 constexpr int kTileH = 32;        // output rows per tile (48: 4 % slower, 3 waves/SIMD)
@@ -148,7 +148,6 @@ constexpr uint32_t kSelW = 0x0C0C0504u;
 // This replaces a second matching pass over the mirrored pair.
 // NW = kWideTile (16 waves, one workgroup per CU) for launches of few tiles: the d range of a tile is
 // split over 4x the waves, so a launch of ~1 round of workgroups runs in ~4 short rounds instead.
-constexpr int kWideTile = 16;
 template <int R, int DMAX, bool RIGHT, int NW = kWavesD<RIGHT, R, DMAX>>
 __global__ __launch_bounds__((64 * NW), (NW == kWideTile ? 4 : NW == 6 ? 3 : kMinWavesPerEU<RIGHT, R>))
 void box_match_kernel(MatchArgs a, int tiles_x, int tiles_y) {
@@ -598,14 +597,18 @@ struct RightOut {
     uint32_t* rkeys;  // slice mode: raw right keys [batch][H][W] instead of dR (check 0, right null)
 };
 
-// Launches of more tiles than CUs but at most kMidTilesPerCu tiles per CU (batch 1 of a mid-size frame) take 8-wave
-// tiles, the d pairs split over twice the waves: the last round of tiles ends sooner.  Same box, device resident,
-// batch 1 (profiles/microbench/r04_box_mid_tiles_latency.txt): 960x540 D=128 47.5 -> 39.7 us, 320x240 D=32
-// 16.7 -> 13.6, 1080p D=128 88.5 -> 86.3; maps identical.
-constexpr int kMidTilesPerCu = 8;
+// the left-only kernel on NW-wave tiles
+template <int R, int DMAX, int NW>
+hipError_t launch_left(const MatchArgs& a, int64_t blocks, int tiles_x, int tiles_y, hipStream_t s) {
+    using G = Geo<R, DMAX, NW>;
+    hipLaunchKernelGGL((box_match_kernel<R, DMAX, false, NW>), dim3((unsigned)blocks), dim3(64 * NW),
+                       (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
+    return hipGetLastError();
+}
 
 // box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the kernels of this file, 2 the matrix-pipe kernel
-// (bm_box_mfma.hip) at any launch size; outside that kernel's scope (the right view, r = 0, r > 7) 2 is 0
+// (bm_box_mfma.hip) at any launch size; outside that kernel's scope (the right view, r = 0, r > 7) 2 is 0.  Which
+// kernel the left-only pass takes is box_tile_kernel's (bm_box_plan.h)
 template <int R, int DMAX, bool RIGHT>
 hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel,
                      int box_workgroups = 0) {
@@ -625,39 +628,24 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
                            (size_t)((a.W + 3) & ~3), s, a.rpart, tiles_x, tiles_y, G::TW, G::PWP, DMAX,
                            a.d_hi - a.d_lo, a.W, a.H, ro->check, a.disp, a.out_pitch, a.out_frame_stride, ro->right,
                            ro->mask, ro->pitch, ro->stride, ro->rkeys, a.d_lo);
+        return hipGetLastError();
     } else {
-        // no more tiles than CUs (a small frame, batch 1): 16 waves per tile, >= 2 d-pairs each, so every
-        // CU runs 16 waves instead of <= 4 (R <= 7: the wide-radius kernels need > 128 VGPRs).  Beyond
-        // one tile per CU the 4-wave kernel wins: with one 16-wave workgroup per CU a tile's staging
-        // overlaps no other tile's compute (1080p batch 1: 102.8 vs 87.8 us).
-        const int npairs = ((a.d_hi - a.d_lo + kChunk - 1) & ~(kChunk - 1)) / 2;
-        const bool mfma_ok = R >= 1 && R <= kMaxFastRadius && box_mfma_scope(a);
-        if (mfma_ok && box_kernel == 2) return launch_box_match_mfma(a, batch, s, box_workgroups);
-        const int cus = device_cus();
-        const int64_t mid_blocks = (int64_t)kMidTilesPerCu * cus;
-        if constexpr (!kWideR<R>) {
-            if (blocks <= cus && npairs >= 2 * kWideTile) {
-                using GW = Geo<R, DMAX, kWideTile>;
-                hipLaunchKernelGGL((box_match_kernel<R, DMAX, false, kWideTile>), dim3((unsigned)blocks),
-                                   dim3(64 * kWideTile), (size_t)GW::LDS_BYTES, s, a, tiles_x, tiles_y);
-                return hipGetLastError();
-            }
-            if (blocks <= mid_blocks && npairs >= 16) {
-                using GM = Geo<R, DMAX, 8>;
-                hipLaunchKernelGGL((box_match_kernel<R, DMAX, false, 8>), dim3((unsigned)blocks), dim3(64 * 8),
-                                   (size_t)GM::LDS_BYTES, s, a, tiles_x, tiles_y);
-                return hipGetLastError();
-            }
+        const BoxTileKernel k = box_tile_kernel(R, a.d_hi - a.d_lo, blocks, device_cus(), box_kernel,
+                                                box_mfma_scope(box_geom(a, batch), a.valid_mode));
+        switch (k) {
+            case BoxTileKernel::Matrix: return launch_box_match_mfma(a, batch, s, box_workgroups);
+            case BoxTileKernel::Wide16:
+            case BoxTileKernel::Mid8:
+                if constexpr (kWideR<R>) {
+                    return hipErrorInvalidValue;   // never the plan's answer past kMaxFastRadius
+                } else {
+                    return k == BoxTileKernel::Wide16 ? launch_left<R, DMAX, kWideTile>(a, blocks, tiles_x, tiles_y, s)
+                                                      : launch_left<R, DMAX, kMidTile>(a, blocks, tiles_x, tiles_y, s);
+                }
+            case BoxTileKernel::Plain: break;
         }
-        // launches past the 8-wave tiles' range (a batch of frames: the throughput path) take the matrix-pipe
-        // kernel: 1080p D = 128 r = 5, 128 frames per launch, 6.91 -> 6.04 ms; D = 256 x 32 frames 3.51 -> 2.94;
-        // 4K D = 192 x 8 frames 2.51 -> 2.10; batch 1 stays on the 8-wave tiles (0.070 against 0.071 ms)
-        // (profiles/microbench/box_mfma_headline_ab.txt)
-        if (mfma_ok && box_kernel == 0 && blocks > mid_blocks) return launch_box_match_mfma(a, batch, s, box_workgroups);
-        hipLaunchKernelGGL((box_match_kernel<R, DMAX, false>), dim3((unsigned)blocks), dim3(64 * kWaves<false, R>),
-                           (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
+        return launch_left<R, DMAX, kWaves<false, R>>(a, blocks, tiles_x, tiles_y, s);
     }
-    return hipGetLastError();
 }
 
 template <int R, bool RIGHT>

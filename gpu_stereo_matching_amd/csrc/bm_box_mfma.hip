@@ -766,35 +766,12 @@ __global__ __launch_bounds__(kThreads, 3) void box_mfma_tile_kernel(MatchArgs a,
     box_mfma_tiles<R, DMAX, 1, false>(a, tiles_x, tiles_y, 1, 0);
 }
 
-constexpr int kMaxDevices = 64;
 // Workgroups launched per resident slot in auto mode.  One per slot is the slowest form (1080p D = 128 r = 5 x 128
 // frames: 5.40 ms against 5.07 for one tile per workgroup): the three waves of a SIMD keep their age order for the
 // whole launch and the launch ends with the youngest.  Shorter ranges let the dispatcher even that out: 2 / 4 / 8 / 16
 // per slot 5.14 / 4.94 / 4.98 / 4.94 ms, D = 256 x 32 frames 2.48 / 2.42 / 2.39 / 2.39
 // (profiles/microbench/box_mfma_rows_ab.txt)
 constexpr int kRangesPerSlot = 16;
-
-// workgroups of this instantiation the current device holds at once: the occupancy query times its CUs, asked once
-// per device and instantiation
-template <int R, int DMAX, int NP>
-hipError_t resident_workgroups(int* out) {
-    static std::atomic<int> slots[kMaxDevices];   // 0: not asked yet
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < kMaxDevices;
-    int v = cached ? slots[dev].load(std::memory_order_relaxed) : 0;
-    if (v == 0) {
-        int per_cu = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, box_mfma_kernel<R, DMAX, NP>, kThreads,
-                                                         (size_t)MG<R, DMAX, NP>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        v = (per_cu > 0 ? per_cu : 1) * device_cus();
-        if (cached) slots[dev].store(v, std::memory_order_relaxed);
-    }
-    *out = v;
-    return hipSuccess;
-}
 
 // workgroups: 0 auto (kRangesPerSlot ranges of tiles per resident workgroup slot), n >= 1 that many, at most one
 // per tile
@@ -817,7 +794,8 @@ hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgrou
     }
     if (n == 0) {
         int slots = 0;
-        hipError_t e = resident_workgroups<R, DMAX, NP>(&slots);
+        hipError_t e = resident_workgroups(reinterpret_cast<const void*>(&box_mfma_kernel<R, DMAX, NP>), kThreads,
+                                           (size_t)G::LDS_BYTES, &slots);
         if (e != hipSuccess) return e;
         n = (int64_t)slots * kRangesPerSlot;
     }
@@ -849,13 +827,8 @@ hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s, int workgroups
 
 }  // namespace
 
-bool box_mfma_scope(const MatchArgs& a) {
-    return a.radius >= 1 && a.radius <= kMaxFastRadius && a.valid_mode == 0 && a.d_lo >= 0 && a.d_hi > a.d_lo &&
-           a.d_hi <= kMaxDisp;
-}
-
 hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
-    if (!box_mfma_scope(a)) return hipErrorInvalidValue;
+    if (!box_mfma_scope(box_geom(a, batch), a.valid_mode)) return hipErrorInvalidValue;
     return with_radius<1, kMaxFastRadius>(a.radius, hipErrorInvalidValue,
                                           [&](auto r) { return launch_r<decltype(r)::value>(a, batch, s, workgroups); });
 }

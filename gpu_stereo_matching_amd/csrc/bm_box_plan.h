@@ -11,6 +11,8 @@
 
 namespace sm {
 
+constexpr int kMaxDisp = 256;      // uint8 output / 8-bit d field of the packed key
+constexpr int kMaxFastRadius = 7;  // u16 packed sums stay < 2^16 up to r = 7 (15*15*255 = 57375)
 // fused tile kernel (bm_box.hip): u16 packed column prefixes stay < 2^16 up to r = 15 ((32 + 30) * 255 = 15810);
 // r 8..15 sum the window's two halves in u32
 constexpr int kMaxBoxRadius = 15;
@@ -74,6 +76,46 @@ inline size_t box_right_partial_bytes(int W, int H, int radius, int D, int batch
     const int TW = box_tile_width(radius);
     const size_t tiles = (size_t)((W + TW - 1) / TW) * ((H + kBoxTileH - 1) / kBoxTileH);
     return tiles * (size_t)batch * kBoxTileH * box_partial_pitch(radius, box_dmax(D)) * 4;
+}
+
+// Which kernel a left-only tile pass launches (launch_rd, bm_box.hip).
+// the matrix-pipe kernel's scope (bm_box_mfma.hip): the left view alone, radius 1..kMaxFastRadius, valid_mode 0
+inline bool box_mfma_scope(const BoxGeom& g, int valid_mode) {
+    return g.radius >= 1 && g.radius <= kMaxFastRadius && valid_mode == 0 && g.d_lo >= 0 && g.d_hi > g.d_lo &&
+           g.d_hi <= kMaxDisp;
+}
+enum class BoxTileKernel {
+    Plain,    // 4 waves per tile
+    Mid8,     // 8 waves
+    Wide16,   // kWideTile waves
+    Matrix,   // bm_box_mfma.hip
+};
+// Wide16: no more tiles than CUs (a small frame, batch 1): 16 waves per tile, >= 2 d-pairs each, so every CU runs
+// 16 waves instead of <= 4 (r <= 7: the wide-radius kernels need > 128 VGPRs).  Beyond one tile per CU the 4-wave
+// kernel wins: with one 16-wave workgroup per CU a tile's staging overlaps no other tile's compute (1080p batch 1:
+// 102.8 vs 87.8 us).
+constexpr int kWideTile = 16;
+// Mid8: launches of more tiles than CUs but at most kMidTilesPerCu tiles per CU (batch 1 of a mid-size frame) take
+// 8-wave tiles, the d pairs split over twice the waves: the last round of tiles ends sooner.  Same box, device
+// resident, batch 1 (profiles/microbench/r04_box_mid_tiles_latency.txt): 960x540 D=128 47.5 -> 39.7 us, 320x240 D=32
+// 16.7 -> 13.6, 1080p D=128 88.5 -> 86.3; maps identical.
+constexpr int kMidTile = 8, kMidTilesPerCu = 8;
+// Matrix: launches past the 8-wave tiles' range (a batch of frames: the throughput path): 1080p D = 128 r = 5, 128
+// frames per launch, 6.91 -> 6.04 ms; D = 256 x 32 frames 3.51 -> 2.94; 4K D = 192 x 8 frames 2.51 -> 2.10; batch 1
+// stays on the 8-wave tiles (0.070 against 0.071 ms) (profiles/microbench/box_mfma_headline_ab.txt)
+// dspan: d_hi - d_lo; tiles: tiles_x * tiles_y * batch; box_kernel (SM_PARAM_BOX_KERNEL): 0 auto, 1 the kernels of
+// bm_box.hip, 2 the matrix-pipe kernel at any launch size; outside that kernel's scope 2 is 0
+constexpr BoxTileKernel box_tile_kernel(int radius, int dspan, int64_t tiles, int cus, int box_kernel,
+                                        bool in_matrix_scope) {
+    const int npairs = ((dspan + kBoxChunk - 1) & ~(kBoxChunk - 1)) / 2;
+    const int64_t mid_tiles = (int64_t)kMidTilesPerCu * cus;
+    if (in_matrix_scope && box_kernel == 2) return BoxTileKernel::Matrix;
+    if (radius <= kMaxFastRadius) {
+        if (tiles <= cus && npairs >= 2 * kWideTile) return BoxTileKernel::Wide16;
+        if (tiles <= mid_tiles && npairs >= 2 * kMidTile) return BoxTileKernel::Mid8;
+    }
+    if (in_matrix_scope && box_kernel == 0 && tiles > mid_tiles) return BoxTileKernel::Matrix;
+    return BoxTileKernel::Plain;
 }
 
 // Wide path: frames per vsum / hwta launch pair: enough row blocks for ~32 per CU (1080 rows of one 1080p frame

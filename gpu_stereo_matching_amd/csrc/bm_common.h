@@ -4,7 +4,12 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <type_traits>
+
+#include "bm_box_plan.h"   // kMaxDisp, kMaxFastRadius and the box pass's predicates
 
 namespace sm {
 
@@ -25,6 +30,10 @@ struct MatchArgs {
     uint32_t* keys;         // optional: packed keys [batch][H][W] (multi-GPU slice reduction)
     uint32_t* rpart;        // fused right view: per-tile right-key partials (box_right_partial_bytes, bm_box_plan.h)
 };
+// the pass as the plan headers take it
+inline BoxGeom box_geom(const MatchArgs& a, int batch) {
+    return BoxGeom{a.W, a.H, a.pitch, a.radius, a.d_lo, a.d_hi, batch};
+}
 
 // The CU count of the current device, asked once per device index: the handles of a group on several devices size
 // each launch by their own device (256 when the query fails).
@@ -42,6 +51,29 @@ inline int device_cus() {
     return cus;
 }
 
+// Workgroups of `kernel` (at `threads` threads and `lds_bytes` of dynamic LDS each) that the current device holds at
+// once: the occupancy query's answer (at least 1) times device_cus(), asked once per distinct kernel, launch shape
+// and device.  Any thread may call it (group members launch from their own).  A failed query is returned and not
+// remembered: the caller decides what to launch without it.
+inline hipError_t resident_workgroups(const void* kernel, int threads, size_t lds_bytes, int* out) {
+    static std::mutex lock;
+    static std::map<std::tuple<const void*, int, size_t, int>, int> known;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const auto key = std::make_tuple(kernel, threads, lds_bytes, dev);
+    const std::lock_guard<std::mutex> hold(lock);
+    auto it = known.find(key);
+    if (it == known.end()) {
+        int per_cu = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes);
+        if (e != hipSuccess) return e;
+        it = known.emplace(key, (per_cu > 0 ? per_cu : 1) * device_cus()).first;
+    }
+    *out = it->second;
+    return hipSuccess;
+}
+
 // f(std::integral_constant<int, R>{}) for the R in [LO, HI] that equals r (the radius as a kernel's template
 // argument), else `fallback`
 template <int LO, int HI, class T, class F>
@@ -54,7 +86,6 @@ T with_radius(int r, T fallback, F&& f) {
     }
 }
 
-constexpr int kMaxDisp = 256;      // uint8 output / 8-bit d field of the packed key
 constexpr int kNumXcd = 8;         // MI355X: 8 XCDs, each with its own L2
 
 // Workgroups are dispatched round-robin over the XCDs (blockIdx % 8).  Remapping so that XCD k
@@ -81,7 +112,6 @@ __device__ __forceinline__ uint32_t ld_image_u32(const uint8_t* p, int y, int x,
         if (x + b >= 0 && x + b < W) v |= (uint32_t)row[x + b] << (8 * b);
     return v;
 }
-constexpr int kMaxFastRadius = 7;  // u16 packed sums stay < 2^16 up to r = 7 (15*15*255 = 57375)
 
 // Host-side launchers (bm_box.hip, bm_aux.hip).  Which box launcher a pass takes, and the workspace sizes named
 // below, are bm_box_plan.h's (plan_box_pass); a launcher checks only its own arguments.
@@ -92,8 +122,7 @@ constexpr int kMaxFastRadius = 7;  // u16 packed sums stay < 2^16 up to r = 7 (1
 // tiles: 0 auto, n >= 1 that many (at most one per tile)
 hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel = 0, int box_workgroups = 0);
 // the plain box pass with both window sums on the matrix pipe: radius 1..kMaxFastRadius, valid_mode 0, no right
-// view; bit-exact with launch_box_match.  hipErrorInvalidValue outside box_mfma_scope
-bool box_mfma_scope(const MatchArgs& a);
+// view; bit-exact with launch_box_match.  hipErrorInvalidValue outside box_mfma_scope (bm_box_plan.h)
 hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups = 0);
 // any radius: the direct window sum per (pixel, d), straight from the reference formulation; not a performance path
 hipError_t launch_box_match_generic(const MatchArgs& a, int batch, hipStream_t s);

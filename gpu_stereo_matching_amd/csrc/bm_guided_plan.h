@@ -9,7 +9,7 @@
 
 namespace sm {
 
-// the kernel's radii and disparities (bm_guided.hip checks them against kMaxFastRadius and kMaxDisp, bm_common.h)
+// the kernel's radii and disparities (bm_guided.hip checks them against kMaxFastRadius and kMaxDisp, bm_box_plan.h)
 constexpr int kMaxGuidedRadius = 7;
 constexpr int kMaxGuidedDisp = 256;
 

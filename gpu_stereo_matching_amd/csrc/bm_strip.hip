@@ -21,18 +21,15 @@
 // as many as the resident workgroups allow in one round (4 waves per SIMD: <= 128 VGPRs).
 // 1080p, D = 128, 8 frames per call (us per frame, MI355X, same box, against the separable path's 234-237):
 // r = 16 141.9, r = 20 150.7, r = 25 180.2, r = 31 203.9, r = 37 223.4.
-#include <algorithm>
 #include <type_traits>
 
-#include "bm_box_plan.h"
 #include "bm_common.h"
+#include "bm_strip_plan.h"
 
 namespace sm {
 namespace {
 
-constexpr int kSC = 128;      // input columns per strip
-constexpr int kSP = kSC / 2;  // u16 column pairs per strip row
-constexpr int kSQ = kSC / 4;  // 4-column groups per strip
+// the strip's columns (kSC, kSP, kSQ), its LDS layout, interior test and row bands: bm_strip_plan.h
 constexpr int kNT = 256;      // max threads per workgroup (4 waves: d spans up to 256)
 constexpr int kWPE = 4;       // waves per SIMD the register budget is sized for
 constexpr int kLA = 1;        // 4-column groups whose LDS reads are in flight ahead of the one being summed
@@ -63,13 +60,6 @@ __device__ __forceinline__ uint32_t dpp_min(uint32_t keep, uint32_t send) {
     return min(keep, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)send, CTRL, 0xF, 0xF, false));
 }
 
-// R staged words per copy of a row: columns rb0 .. rb0 + DP - d_lo + kSC + 3 (d_lo rounded down to 4; the lanes
-// read staged columns DP - d .. DP - d + 127) as u16 pairs; copies r_stride words apart, = 16 mod 32, so that the
-// lanes reading copy 0 (even DP - d) and copy 1 (odd) fall on disjoint halves of the banks
-constexpr int r_words(int DP, int d_lo) { return (DP - (d_lo & ~3) + kSC + 4) / 2; }
-constexpr int r_stride(int RW) { return ((RW + 15) & ~31) + 16; }
-constexpr int stage_bytes(int RS) { return 2 * kSP * 4 + 2 * 2 * RS * 4; }
-
 // RIGHT: the right view too, folded per output row into an LDS row by atomic min (C_R(u, d) = C_L(u + d, d) for
 // u = x - d >= 0, StereoHelper.cpp:156-180, as the separable path's hwta kernel) and flushed into rk, the frame's
 // right keys [batch][H][W] (filled with ~0 by the caller), by global atomic min (strips overlap in u)
@@ -80,8 +70,9 @@ __global__ __launch_bounds__(kNT, kWPE) void strip_kernel(const uint8_t* __restr
                                                     int DP, int RW, int RS, int nw, uint32_t seed, uint32_t thresh,
                                                     uint8_t* __restrict__ disp, int opitch, int64_t ostride,
                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ rk) {
-    constexpr int SW = kSC - 2 * R;            // output columns of the strip
+    constexpr int SW = strip_out_cols(R);      // output columns of the strip
     constexpr int NG = (SW + 7) / 8;           // groups of 8 outputs
+    // the layout strip_lds sizes (bm_strip_plan.h: wmin_off, rrow_off; held to these lines by tests/test_strip_plan.py)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int BUF = stage_bytes(RS);           // one step: L in/out as u16 column pairs, R in/out as two copies
     const int nt = 64 * nw;                    // threads (blockDim.x, kept in an SGPR)
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(kNT, kWPE) void strip_kernel(const uint8_t* __restr
     const uint32_t s0 = live ? 0u : (1u << 23);
 
     // strip-uniform: every column of the strip >= every d and inside the frame (no AD masks), and every output
-    // inside the frame with every d valid (no key masks)
+    // inside the frame with every d valid (no key masks): strip_interior (bm_strip_plan.h), written out
     const bool col_ok = cs0 >= d_hi - 1 && cs0 + kSC <= W;
     // (vm = valid_mode: 0 d <= W - x, Device.cu:44; 1 the mirrored right view's d <= x)
     const bool out_ok = x0 + SW <= W && (vm == 0 ? (d_hi - 1) <= W - (x0 + SW - 1) : (d_hi - 1) <= x0);
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(kNT, kWPE) void strip_kernel(const uint8_t* __restr
     // no step waits on a global load
     const int ng = RW / 2;                      // 4-column groups per R row
     const int nL = 2 * kSQ, nItems = nL + 2 * ng;
-    constexpr int kPF = 3;                      // items per thread: 64 + 2 ceil((nd + 135) / 4) <= 3 * 64 nw
+    constexpr int kPF = kStripStageItems;       // items per thread: nItems <= kPF * nt (tests/test_strip_plan.py)
     uint32_t pw[kPF], pw2[kPF];
     auto fetch = [&](int yin, int yout) SM_INL {
 #pragma unroll
@@ -476,76 +467,23 @@ __global__ __launch_bounds__(kNT, kWPE) void strip_kernel(const uint8_t* __restr
 #endif
 }
 
-// Row bands, one round of workgroups (a second, partial round would leave most of the chip idle while it runs):
-// interior strips in nb bands, edge strips in nbe, chosen to minimise the longer of the two band walks, a band of
-// height h costing (h + 2r) row steps (its first 2r steps only build V), an edge step kEdgeCost % of an
-// interior one (the masked body), over the (nb, nbe) whose workgroups all fit at once.
-constexpr int kEdgeCost = 150;
-constexpr int kFill = 100;   // percent of the resident workgroups the bands aim at
-struct StripGrid {
-    int EL, NI, ER;   // left edge, interior and right edge strips
-    int nb, nbe;      // bands per interior / edge strip
-};
-
-StripGrid strip_grid(const MatchArgs& a, int R, int SW, int frames, int resident) {
-    StripGrid g{0, 0, 0, 1, 1};
-    const int strips = (a.W + SW - 1) / SW;
-    // the kernel's col_ok && out_ok, per strip: the interior strips are one contiguous run
-    auto interior = [&](int st) {
-        const int x0 = st * SW, cs0 = x0 - R;
-        return cs0 >= a.d_hi - 1 && cs0 + kSC <= a.W && x0 + SW <= a.W &&
-               (a.valid_mode == 0 ? (a.d_hi - 1) <= a.W - (x0 + SW - 1) : (a.d_hi - 1) <= x0);
-    };
-    while (g.EL < strips && !interior(g.EL)) ++g.EL;
-    g.NI = 0;
-    while (g.EL + g.NI < strips && interior(g.EL + g.NI)) ++g.NI;
-    g.ER = strips - g.EL - g.NI;
-    const int ne = g.EL + g.ER;
-    const int nb_max = std::max(1, a.H / (4 * R)), nbe_max = std::max(1, a.H / (2 * R));
-    int64_t best = -1;
-    for (int nb = 1; nb <= (g.NI ? nb_max : 1); ++nb)
-        for (int nbe = 1; nbe <= (ne ? nbe_max : 1); ++nbe) {
-            const int64_t blocks = ((int64_t)ne * nbe + (int64_t)g.NI * nb) * frames;
-            if (blocks > resident && !(nb == 1 && nbe == 1)) continue;
-            const int64_t ti = g.NI ? (int64_t)((a.H + nb - 1) / nb + 2 * R) * 100 : 0;
-            const int64_t te = ne ? (int64_t)((a.H + nbe - 1) / nbe + 2 * R) * kEdgeCost : 0;
-            const int64_t t = std::max(ti, te);
-            if (best < 0 || t < best) {
-                best = t;
-                g.nb = nb;
-                g.nbe = nbe;
-            }
-        }
-    return g;
-}
-
+// the LDS layout and the bands are bm_strip_plan.h's; the bands fill the workgroups resident at once (one per CU
+// where the occupancy query fails)
 template <int R, bool RIGHT>
 hipError_t launch_strip_r(const MatchArgs& a, int batch, hipStream_t s, uint32_t* rk) {
-    constexpr int SW = kSC - 2 * R;
-    const int nd = a.d_hi - a.d_lo;
-    const int nw = (nd + 63) / 64;
-    const int DP = ((a.d_hi - 1) + 3) & ~3;
-    const int RW = r_words(DP, a.d_lo), RS = r_stride(RW);
-    const size_t lds = (size_t)2 * stage_bytes(RS) + (size_t)2 * nw * ((SW + 7) / 8) * 8 * 4 +
-                       (RIGHT ? (size_t)2 * (SW + DP) * 4 : 0);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, strip_kernel<R, RIGHT>, 64 * nw, lds) != hipSuccess ||
-        per_cu <= 0)
-        per_cu = 1;
-    const StripGrid g = strip_grid(a, R, SW, batch, per_cu * device_cus() * kFill / 100);
+    const StripLds l = strip_lds(R, a.d_lo, a.d_hi, RIGHT);
+    int resident = 0;
+    if (resident_workgroups(reinterpret_cast<const void*>(&strip_kernel<R, RIGHT>), 64 * l.nw, (size_t)l.bytes,
+                            &resident) != hipSuccess)
+        resident = device_cus();
+    const StripGrid g = strip_grid(box_geom(a, batch), a.valid_mode, resident);
     const int64_t nblk = (int64_t)(g.EL + g.ER) * g.nbe + (int64_t)g.NI * g.nb;
     if (nblk > 0x7FFFFFFF || batch > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((strip_kernel<R, RIGHT>), dim3((unsigned)nblk, 1u, (unsigned)batch), dim3(64 * nw), lds, s,
-                       a.left, a.right, a.frame_stride, a.W, a.H, a.pitch, a.d_lo, a.d_hi, g.EL, g.NI, g.nb, g.nbe,
-                       a.valid_mode, DP, RW, RS, nw, a.seed_key, a.thresh_key, a.disp, a.out_pitch, a.out_frame_stride,
-                       a.keys, rk);
+    hipLaunchKernelGGL((strip_kernel<R, RIGHT>), dim3((unsigned)nblk, 1u, (unsigned)batch), dim3(64 * l.nw),
+                       (size_t)l.bytes, s, a.left, a.right, a.frame_stride, a.W, a.H, a.pitch, a.d_lo, a.d_hi, g.EL,
+                       g.NI, g.nb, g.nbe, a.valid_mode, l.DP, l.RW, l.RS, l.nw, a.seed_key, a.thresh_key, a.disp,
+                       a.out_pitch, a.out_frame_stride, a.keys, rk);
     return hipGetLastError();
-}
-
-// what the kernel takes: the plan's strip_path (bm_box_plan.h) and a known valid_mode
-bool strip_args_ok(const MatchArgs& a, int batch) {
-    return strip_path(BoxGeom{a.W, a.H, a.pitch, a.radius, a.d_lo, a.d_hi, batch}) && batch > 0 &&
-           (a.valid_mode == 0 || a.valid_mode == 1);
 }
 
 template <bool RIGHT>
@@ -559,13 +497,14 @@ hipError_t dispatch_strip(const MatchArgs& a, int batch, hipStream_t s, uint32_t
 
 #ifndef SM_STRIP_RIGHT_TU
 hipError_t launch_box_match_strip(const MatchArgs& a, int batch, hipStream_t s) {
-    if (!strip_args_ok(a, batch)) return hipErrorInvalidValue;
+    if (!strip_args_ok(box_geom(a, batch), a.valid_mode)) return hipErrorInvalidValue;
     return dispatch_strip<false>(a, batch, s, nullptr);
 }
 #else
 // bm_strip_lr.hip: the instantiations with the right view, compiled in their own translation unit
 hipError_t launch_box_match_strip_lr(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s) {
-    if (!strip_args_ok(a, batch) || a.valid_mode != 0 || a.d_lo != 0 || !right_keys) return hipErrorInvalidValue;
+    if (!strip_args_ok(box_geom(a, batch), a.valid_mode) || a.valid_mode != 0 || a.d_lo != 0 || !right_keys)
+        return hipErrorInvalidValue;
     return dispatch_strip<true>(a, batch, s, right_keys);
 }
 #endif

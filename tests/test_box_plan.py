@@ -1,7 +1,7 @@
 """plan_box_pass (csrc/bm_box_plan.h): which kernels a box-aggregation pass runs and the workspace it takes, on the
 CPU.  The header is built with g++ alone (tests/native/box_plan_shim.cpp) and compared with the selection rules
 restated here: tile kernels up to r = 15, the strip kernel at r 16..37, the separable wide path, the direct kernel,
-and where the right view comes from."""
+and where the right view comes from; and box_tile_kernel, which kernel a left-only tile pass launches."""
 import ctypes
 import itertools
 import os
@@ -25,7 +25,7 @@ BATCHES = (1, 3)
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
+def lib(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("g++ absent")
     out = str(tmp_path_factory.mktemp("plan") / "libbox_plan_shim.so")
@@ -34,7 +34,12 @@ def plan(tmp_path_factory):
     lib = ctypes.CDLL(out)
     lib.box_plan.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_ulonglong)]
     lib.box_plan.restype = None
+    lib.box_tile_kernel.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [ctypes.c_int] * 3
+    return lib
 
+
+@pytest.fixture(scope="module")
+def plan(lib):
     def call(W, H, pitch, radius, d_lo, d_hi, batch, want):
         o = (ctypes.c_ulonglong * 5)()
         lib.box_plan(W, H, pitch, radius, d_lo, d_hi, batch, want, o)
@@ -124,3 +129,49 @@ def test_pinned_workspace_sizes(plan):
         p = plan(1920, 1080, 1920, 40, 0, 128, 8, want)
         assert p["left"] == WIDE
         assert p["vol"] == 8 * 128 * 1920 * 1080 * 2 == 4246732800 and p["rpart"] == 0
+
+
+PLAIN, MID8, WIDE16, MATRIX = 0, 1, 2, 3        # BoxTileKernel
+
+
+def tile_kernel(r, span, tiles, cus, box_kernel, scope):
+    """Which kernel a left-only tile pass launches: the forced matrix kernel inside its scope first, then 16-wave
+    tiles (r <= 7, at most one tile per CU, >= 32 d pairs), 8-wave tiles (r <= 7, at most 8 tiles per CU, >= 16
+    pairs), the matrix kernel by itself past 8 tiles per CU, else the 4-wave kernel."""
+    npairs = ((span + 7) & ~7) // 2
+    if scope and box_kernel == 2:
+        return MATRIX
+    if r <= 7:
+        if tiles <= cus and npairs >= 32:
+            return WIDE16
+        if tiles <= 8 * cus and npairs >= 16:
+            return MID8
+    if scope and box_kernel == 0 and tiles > 8 * cus:
+        return MATRIX
+    return PLAIN
+
+
+def test_tile_kernel_follows_the_rule(lib):
+    seen = set()
+    for cus in (256, 7):
+        for r, span, tiles, box_kernel, scope in itertools.product(
+                (0, 1, 7, 8, 15), (8, 31, 32, 64, 128), (cus - 1, cus, cus + 1, 8 * cus, 8 * cus + 1), (0, 1, 2),
+                (0, 1)):
+            got = lib.box_tile_kernel(r, span, tiles, cus, box_kernel, scope)
+            assert got == tile_kernel(r, span, tiles, cus, box_kernel, scope), (r, span, tiles, cus, box_kernel, scope)
+            seen.add(got)
+    assert seen == {PLAIN, MID8, WIDE16, MATRIX}
+    # the headline (1080p D = 128 r = 5: 36 x 34 tiles of 54 x 32) on 256 CUs: batch 1 on 8-wave tiles, a batch of
+    # frames on the matrix kernel unless the VALU kernels are forced; 2^31 - 1 tiles stay in range
+    assert lib.box_tile_kernel(5, 128, 36 * 34, 256, 0, 1) == MID8
+    assert lib.box_tile_kernel(5, 128, 36 * 34 * 8, 256, 0, 1) == MATRIX
+    assert lib.box_tile_kernel(5, 128, 36 * 34 * 8, 256, 1, 1) == PLAIN
+    assert lib.box_tile_kernel(5, 128, 2 ** 31 - 1, 256, 0, 1) == MATRIX
+
+
+def test_matrix_scope(lib):
+    """The matrix-pipe kernel takes the left view at r 1..7, valid_mode 0, slices inside [0, 256]."""
+    for r, (d_lo, d_hi), vm in itertools.product(range(0, 10), ((0, 1), (0, 256), (20, 64), (0, 257), (5, 5), (-1, 8)),
+                                                 (0, 1)):
+        want = 1 <= r <= 7 and vm == 0 and 0 <= d_lo < d_hi <= 256
+        assert bool(lib.box_mfma_scope(r, d_lo, d_hi, vm)) == want, (r, d_lo, d_hi, vm)
