@@ -29,7 +29,7 @@ from .gray import bgr_to_gray  # noqa: F401
 __all__ = [
     "BlockMatcher", "BlockMatcherGroup", "blockMatching_gpu", "block_matching_gpu", "SMError", "synth_pair", "bgr_to_gray",
     "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_COST_CENSUS", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
-    "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes", "to_float",
+    "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes", "speckle_workspace_bytes", "to_float",
 ]
 
 DEFAULT_GUIDED_EPS = 1e-4 * 255.0 * 255.0
@@ -87,6 +87,14 @@ def census_workspace_bytes(width: int, height: int, num_disp: int, radius: int, 
     n = ctypes.c_size_t()
     _capi.check(_capi.load().sm_census_workspace_bytes(width, height, num_disp, radius, _flags(agg, False, False, "census"),
                                                        ctypes.byref(n)))
+    return n.value
+
+
+def speckle_workspace_bytes(width: int, height: int, batch: int = 1) -> int:
+    """Bytes of device workspace the speckle filter takes on its handle for `batch` frames (uint32 labels and
+    counts, 8 B per pixel of the up to 8 frames in flight; sm_speckle_workspace_bytes, host-only)."""
+    n = ctypes.c_size_t()
+    _capi.check(_capi.load().sm_speckle_workspace_bytes(width, height, batch, ctypes.byref(n)))
     return n.value
 
 
@@ -197,6 +205,54 @@ class BlockMatcher:
         a contiguous range of tiles and keeping the right band along a row; at most one per tile, so n >= tiles is one
         tile per workgroup.  Same maps and keys at every n; the VALU kernels ignore it."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_WORKGROUPS, float(n)))
+
+    def set_speckle(self, size: int = 0, range: int = 1):  # noqa: A002  (StereoSGBM's name)
+        """StereoSGBM's speckleWindowSize / speckleRange (SM_PARAM_SPECKLE_SIZE / _RANGE): with size > 0 the
+        whole-frame matching calls (match, match_lr, match_bgr, match_device, match_subpix[_device]) end with the
+        speckle filter: regions of at most `size` pixels whose neighbours differ by at most `range` whole
+        disparities become 0 (and leave the valid mask).  The defaults turn it off.  The row-band, d-slice and
+        slice-key calls refuse a handle whose size is not 0."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SPECKLE_SIZE, float(int(size))))
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SPECKLE_RANGE, float(int(range))))
+
+    def speckle_filter(self, map, max_size: int, max_diff: int, mask=None):  # noqa: A002
+        """OpenCV's filterSpeckles(map, 0, max_size, max_diff) on a host map (sm_speckle_filter_u8 / _u16): a 2-D
+        uint8 or uint16 array in which 0 is invalid.  Returns (filtered copy, mask): the mask is a copy of `mask`
+        (uint8, the map's shape) cleared where pixels were removed, or None when no mask was given."""
+        m = np.array(map, copy=True, order="C")
+        if m.dtype not in (np.uint8, np.uint16) or m.ndim != 2:
+            raise ValueError(f"map: expected a 2-D uint8 or uint16 map, got {m.dtype} {m.shape}")
+        H, W = m.shape
+        k = None
+        if mask is not None:
+            k = np.array(mask, copy=True, order="C")
+            if k.dtype != np.uint8 or k.shape != m.shape:
+                raise ValueError("mask must be a uint8 array of the map's shape")
+        fn = self._lib.sm_speckle_filter_u8 if m.dtype == np.uint8 else self._lib.sm_speckle_filter_u16
+        _capi.check(fn(self._h, m.ctypes.data, W, H, W, int(max_size), int(max_diff),
+                       k.ctypes.data if k is not None else None, W))
+        return m, k
+
+    def speckle_filter_device(self, map_t, max_size: int, max_diff: int, mask=None, stream=None):
+        """Device form of :meth:`speckle_filter` (sm_speckle_filter_device), in place and async on `stream`: map_t a
+        uint8 or int16 (uint16 bit patterns) cuda tensor [H, W] or [B, H, W] with contiguous rows (row and frame
+        strides are passed on); mask: an optional contiguous uint8 tensor of the map's shape, cleared where pixels
+        are removed.  Returns map_t."""
+        import torch
+        if map_t.dtype not in (torch.uint8, torch.int16, torch.uint16) or map_t.dim() not in (2, 3) \
+                or not map_t.is_cuda or map_t.stride(-1) != 1:
+            raise ValueError("map_t must be a uint8 or int16 [H, W] or [B, H, W] device tensor with contiguous rows")
+        if map_t.device.index != self.device:
+            raise ValueError(f"the map must be on cuda:{self.device}, the handle's device")
+        B = 1 if map_t.dim() == 2 else map_t.shape[0]
+        H, W = map_t.shape[-2:]
+        if mask is not None:
+            _check_out(mask, map_t.shape, torch.uint8, map_t.device, "mask")
+        fs = map_t.stride(0) if map_t.dim() == 3 else map_t.stride(-2) * H
+        _capi.check(self._lib.sm_speckle_filter_device(
+            self._h, map_t.data_ptr(), map_t.element_size(), W, H, map_t.stride(-2), B, fs, int(max_size),
+            int(max_diff), mask.data_ptr() if mask is not None else None, self._stream_ptr(stream)))
+        return map_t
 
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
                         lr_check: bool = False) -> np.ndarray:
@@ -803,6 +859,12 @@ class BlockMatcherGroup:
         """BlockMatcher.set_sgm_penalties on every member (agg='sgm' runs in match_batch only: whole frames)."""
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P1, float(int(p1))))
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P2, float(int(p2))))
+
+    def set_speckle(self, size: int = 0, range: int = 1):  # noqa: A002
+        """BlockMatcher.set_speckle on every member: match_batch runs whole frames and honours it; the row-band
+        calls (match, match_lr) and match_dslice refuse a size > 0 and say why."""
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SPECKLE_SIZE, float(int(size))))
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SPECKLE_RANGE, float(int(range))))
 
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
               median: bool = False, cost: str = "ad") -> np.ndarray:

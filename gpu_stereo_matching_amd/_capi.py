@@ -35,6 +35,8 @@ SM_PARAM_SGM_P2 = 5
 SM_PARAM_BOX_KERNEL = 6
 SM_PARAM_UNIQUENESS = 7
 SM_PARAM_BOX_WORKGROUPS = 8
+SM_PARAM_SPECKLE_SIZE = 9
+SM_PARAM_SPECKLE_RANGE = 10
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (
@@ -55,6 +57,7 @@ EXPORTED = (
     "sm_census_volume_device", "sm_census_volume_u8",
     "sm_match_subpix_device", "sm_block_match_subpix_u16", "sm_volume_wta_subpix_device", "sm_reproject_device",
     "sm_reproject_u16",
+    "sm_speckle_workspace_bytes", "sm_speckle_filter_device", "sm_speckle_filter_u8", "sm_speckle_filter_u16",
 )
 
 
@@ -149,6 +152,10 @@ def load(path: str = LIB_PATH):
     L.sm_volume_wta_subpix_device.argtypes = [vp, vp, i, i, i, i, ctypes.c_uint32, u, vp, i, vp, vp, vp]
     L.sm_reproject_device.argtypes = [vp, vp, i, i, i, vp, vp, i, vp]
     L.sm_reproject_u16.argtypes = [vp, vp, i, i, i, vp, vp, i]
+    L.sm_speckle_workspace_bytes.argtypes = [i, i, i, ctypes.POINTER(ctypes.c_size_t)]
+    L.sm_speckle_filter_device.argtypes = [vp, vp, i, i, i, i, i, i64, i, i, vp, vp]
+    L.sm_speckle_filter_u8.argtypes = [vp, vp, i, i, i, i, i, vp, i]
+    L.sm_speckle_filter_u16.argtypes = [vp, vp, i, i, i, i, i, vp, i]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

@@ -224,6 +224,13 @@ hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, i
 // (2r+1)^2 median with replicate borders, radius 1..3 (bm_post.hip)
 hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
                          uint8_t* dst, int dpitch, int64_t dstride, hipStream_t s);
+// speckle filter (bm_speckle.hip), in place on `batch` maps of T = uint8_t or uint16_t (pitch and fstride in
+// elements): every connected region (4-neighbours, both != 0, |a - b| <= max_diff) of at most max_size pixels is set
+// to 0, and `mask` (dense [batch][H][W], may be null) is cleared at the same pixels.  label / count: the planes of
+// plan_speckle(W, H, batch) (bm_speckle_plan.h).  max_size 0 launches nothing.
+template <class T>
+hipError_t launch_speckle(T* map, int W, int H, int pitch, int64_t fstride, int batch, int max_size, int max_diff,
+                          uint8_t* mask, uint32_t* label, uint32_t* count, hipStream_t s);
 
 hipError_t launch_bgr_to_gray(const uint8_t* src, int W, int H, int pitch, int channels, uint8_t* dst, int dpitch,
                               hipStream_t s);

@@ -288,8 +288,13 @@ int group_frame_check(const sm_group* g, const uint8_t* left, const uint8_t* rig
 int group_bands(sm_group* g, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
                 int radius, int num_disp, unsigned flags, uint8_t* disp_out, uint8_t* right_out, uint8_t* mask_out,
                 int out_pitch) {
-    const int rc = group_frame_check(g, left, right, disp_out, width, height, pitch, out_pitch, flags);
+    int rc = group_frame_check(g, left, right, disp_out, width, height, pitch, out_pitch, flags);
     if (rc) return rc;
+    for (const GroupWorker* w : g->w) {   // regions cross the bands
+        rc = speckle_refuse(w->h, "the row-band group call",
+                            "regions cross the bands (sm_group_block_match_batch_u8 runs whole frames)");
+        if (rc) return rc;
+    }
     if (flags & SM_AGG_SGM)   // the vertical paths run through every row of the frame
         return fail(SM_ERR_INVALID_ARG,
                     "SM_AGG_SGM needs whole frames: its vertical paths cross the row bands (sm_group_block_match_batch_u8)");
@@ -413,6 +418,8 @@ SM_API int sm_group_dslice_block_match_u8(sm_group* g, const uint8_t* left, cons
     rc = dslice_check(cfg, flags);
     if (rc) return rc;
     for (GroupWorker* w : g->w) {
+        rc = speckle_refuse(w->h, "the d-slice group call", "the d-slice calls do not run it");
+        if (rc) return rc;
         rc = check_geometry(w->h, width, height, width, radius, num_disp);
         if (rc) return rc;
         rc = check_capacity(w->h, width, height, num_disp);

@@ -157,6 +157,15 @@ VolumeOut subpix_out(uint16_t* disp16, int pitch, int64_t stride, uint16_t* righ
     return o;
 }
 
+// The handle's speckle filter as the sub-pixel calls' last step: on the 1/16-px left map and the mask, regions
+// joined within 16 * range, as StereoSGBM's speckleRange on its 1/16-px map
+int subpix_speckle(WsScope& ws, sm_handle* h, uint16_t* disp16, int W, int H, int pitch, int batch, int64_t stride,
+                   uint8_t* mask) {
+    if (h->speckle_size == 0) return SM_OK;
+    if (!sm::speckle_pass_ok(W, H, batch)) return fail(SM_ERR_INVALID_ARG, "speckle filter: frame %dx%d too large", W, H);
+    return run_speckle(ws, h, disp16, 2, W, H, pitch, batch, stride, h->speckle_size, 16 * h->speckle_range, mask);
+}
+
 }  // namespace
 
 extern "C" {
@@ -205,9 +214,11 @@ SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uin
         return fail(SM_ERR_INVALID_ARG, "frame strides overlap");
     SM_HIP(hipSetDevice(h->device));
     WsScope ws(h, stream_of(stream));
-    return run_volume(ws, h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp,
-                      (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2,
-                      subpix_out(d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, flags));
+    rc = run_volume(ws, h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp,
+                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2,
+                    subpix_out(d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, flags));
+    if (rc) return rc;
+    return subpix_speckle(ws, h, d_disp16, width, height, out_pitch, batch, out_frame_stride, d_mask);
 }
 
 SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
@@ -234,6 +245,8 @@ SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const ui
     rc = run_volume(ws, h, h->d_left, h->d_right, width, height, width, 1, (int64_t)P, radius, num_disp,
                     (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2,
                     subpix_out(dq, width, (int64_t)P, right16_out ? dr : nullptr, mask_out ? dm : nullptr, flags));
+    if (rc) return rc;
+    rc = subpix_speckle(ws, h, dq, width, height, width, 1, (int64_t)P, mask_out ? dm : nullptr);
     if (rc) return rc;
     const size_t row2 = (size_t)width * 2, op2 = (size_t)out_pitch * 2;
     SM_HIP(copy2d(disp16_out, op2, dq, row2, row2, height, hipMemcpyDeviceToHost, s));

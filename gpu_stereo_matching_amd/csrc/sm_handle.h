@@ -14,6 +14,7 @@
 #include "bm_common.h"
 #include "bm_guided.h"
 #include "bm_segtree.h"
+#include "bm_speckle_plan.h"
 
 namespace smh {
 
@@ -100,6 +101,7 @@ struct sm_handle {
     // cost volumes, V planes of the wide path, right keys.  64 readable bytes past the end: box_sad_kernel reads
     // whole 8-byte words at the planes' last bytes
     smh::SharedBuf vol{64};
+    smh::SharedBuf spk;     // speckle filter: u32 labels and u32 counts of the frames in flight (bm_speckle_plan.h)
     // Staging of the host calls, grown on demand.  Only the handle's own stream touches them, in calls that end
     // in a synchronise, so they need no ordering:
     smh::DevBuf maps;   // float maps of the host remap / rectify-map calls
@@ -117,6 +119,8 @@ struct sm_handle {
     int box_kernel = 0;          // SM_PARAM_BOX_KERNEL: 0 auto, 1 VALU kernels, 2 matrix-pipe kernel
     int box_workgroups = 0;      // SM_PARAM_BOX_WORKGROUPS: 0 auto, n >= 1 workgroups per matrix-pipe launch
     int uniqueness = 0;          // SM_PARAM_UNIQUENESS: 0 off, 1..99 the sub-pixel calls' uniqueness ratio
+    int speckle_size = 0;        // SM_PARAM_SPECKLE_SIZE: 0 off, else the largest region the matching calls remove
+    int speckle_range = 1;       // SM_PARAM_SPECKLE_RANGE: whole disparities joined into one region, 0..255
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -199,6 +203,17 @@ int check_geometry(const sm_handle* h, int width, int height, int pitch, int rad
 // SM_ERR_CAPACITY unless the frame fits what sm_create sized the handle for (num_disp 0: a call without one)
 int check_capacity(const sm_handle* h, int width, int height, int num_disp);
 int census_check(int width, int radius, unsigned flags);
+// SM_ERR_INVALID_ARG, naming the speckle filter, when the handle's filter is on: the first check of a call that
+// cannot honour it (`why`: what the filter's regions cross there)
+inline int speckle_refuse(const sm_handle* h, const char* call, const char* why) {
+    if (!h || h->speckle_size == 0) return SM_OK;
+    return fail(SM_ERR_INVALID_ARG, "%s cannot honour the speckle filter (SM_PARAM_SPECKLE_SIZE %d): %s", call,
+                h->speckle_size, why);
+}
+// The speckle filter (bm_speckle.hip) in place on `batch` device maps of elem_bytes 1 or 2, through the handle's
+// `spk` workspace (sm_capi_speckle.hip).  The arguments have been checked.
+int run_speckle(WsScope& ws, sm_handle* h, void* map, int elem_bytes, int W, int H, int pitch, int batch,
+                int64_t fstride, int max_size, int max_diff, uint8_t* mask);
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out);
 
 // SM_AGG_GUIDED's radii (bm_guided_plan.h): every guided entry rejects the others before it takes a workspace

@@ -138,11 +138,19 @@ enum {
                                   kernels.  Other values: SM_ERR_INVALID_ARG */
     SM_PARAM_UNIQUENESS = 7,   /* uniqueness ratio of the sub-pixel calls (sm_match_subpix_device and friends): an
                                   integer 0..99, 0 (default) = off.  Other values: SM_ERR_INVALID_ARG */
-    SM_PARAM_BOX_WORKGROUPS = 8 /* workgroups of a matrix-pipe box launch, each walking a contiguous range of tiles
+    SM_PARAM_BOX_WORKGROUPS = 8, /* workgroups of a matrix-pipe box launch, each walking a contiguous range of tiles
                                   and keeping the right band along a row of tiles: 0 (default) auto, 16 per
                                   workgroup the device holds at once; an integer n >= 1 that many, at most one per
                                   tile (n >= tiles: one tile per workgroup, nothing kept).  The maps and keys do not
                                   depend on it; the VALU kernels ignore it.  Other values: SM_ERR_INVALID_ARG */
+    SM_PARAM_SPECKLE_SIZE = 9, /* StereoSGBM's speckleWindowSize: an integer >= 0 (at most 2^24), 0 (default) = off.
+                                  With a size > 0 every whole-frame matching call ends with the speckle filter
+                                  (sm_speckle_filter_device) on its final left map, after the median and the LR
+                                  check: regions of at most this many pixels become 0.  See "speckle filter" below
+                                  for the calls that honour it and those that refuse it */
+    SM_PARAM_SPECKLE_RANGE = 10 /* StereoSGBM's speckleRange: whole disparities, an integer 0..255, default 1.  The
+                                  8-bit matching calls join neighbours with |a - b| <= range, the 1/16-px calls with
+                                  |a - b| <= 16 * range, as StereoSGBM does on its 1/16-px map */
 };
 
 typedef struct sm_handle sm_handle;
@@ -365,6 +373,45 @@ SM_API int sm_reproject_device(sm_handle *h, const uint16_t *d_disp16, int width
                                const double *Q, float *d_xyz, int xyz_pitch, void *stream);
 SM_API int sm_reproject_u16(sm_handle *h, const uint16_t *disp16, int width, int height, int pitch, const double *Q,
                             float *xyz_out, int xyz_pitch);
+
+/* ---- speckle filter: StereoSGBM's speckleWindowSize / speckleRange (this build's extension) ----
+ * OpenCV's filterSpeckles(img, newVal = 0, maxSpeckleSize, maxDiff) on a uint8 map or a uint16 (1/16 px) map, in
+ * which 0 is this library's invalid value.  All integer:
+ *   a pixel is valid iff its value is != 0; invalid pixels belong to no region and are never changed;
+ *   two 4-neighbours inside the frame are joined iff both are valid and |a - b| <= max_diff, the difference taken
+ *     in 32 bits (255 against 1, or 65535 against 3, does not wrap);
+ *   regions are the connected components of that graph (joining is transitive: a ramp with steps of max_diff is
+ *     one region);
+ *   every pixel of a region of at most max_size pixels is set to 0, and the mask plane, where one is given, is set
+ *     to 0 at exactly those pixels; everything else stays byte for byte, the bytes between width and pitch
+ *     included.  max_size = 0 removes nothing (no launch, no workspace).
+ * sm_speckle_filter_device: in place on `batch` device maps of elem_bytes 1 (uint8) or 2 (uint16), pitch and
+ * frame_stride in elements; d_mask: dense [batch][height][width] or NULL; asynchronous on `stream`.  Every argument
+ * is checked before the device is touched: elem_bytes, max_size >= 0, 0 <= max_diff <= 255 / 65535, pitch >= width,
+ * the handle's capacity.  The frames of a batch run in groups of up to 8, through sm_speckle_workspace_bytes() of
+ * the handle: uint32 labels and uint32 counts, 8 B per pixel of a frame in the group.
+ * sm_speckle_workspace_bytes: host-only (no device, no handle).
+ * sm_speckle_filter_u8 / _u16: the same on one host frame (pitch in elements, mask_pitch in bytes; mask may be
+ * NULL), synchronous.
+ * With SM_PARAM_SPECKLE_SIZE > 0 the filter is the last step, after the median and the LR check, of
+ * sm_block_match_u8, sm_block_match_lr_u8 (whose valid mask is cleared at the removed pixels too; the right map is
+ * untouched), sm_block_match_bgr_u8, sm_match_device and sm_group_block_match_batch_u8 for every aggregation and
+ * flag, and of sm_match_subpix_device / sm_block_match_subpix_u16 on the 1/16-px left map and the mask.  Calls
+ * that cannot honour it return SM_ERR_INVALID_ARG, with a message naming the speckle filter, before any device
+ * work: the row-band group calls (regions cross the bands), sm_group_dslice_block_match_u8 and
+ * sm_dslice_rehearse_u8, and the slice-key calls (sm_slice_keys_device, sm_guided_slice_keys_device,
+ * sm_slice_keys_lr_device).  The segment-tree calls do not apply it: their maps are scaled by `scale`.
+ * Parity with OpenCV's filterSpeckles is by construction of the rule above (its flood fill compares each popped
+ * pixel with its neighbours, so its regions are these components whatever the visiting order); it is not pinned
+ * by a test against OpenCV. */
+SM_API int sm_speckle_workspace_bytes(int width, int height, int batch, size_t *bytes);
+SM_API int sm_speckle_filter_device(sm_handle *h, void *d_map, int elem_bytes, int width, int height, int pitch,
+                                    int batch, int64_t frame_stride, int max_size, int max_diff, uint8_t *d_mask,
+                                    void *stream);
+SM_API int sm_speckle_filter_u8(sm_handle *h, uint8_t *map, int width, int height, int pitch, int max_size,
+                                int max_diff, uint8_t *mask, int mask_pitch);
+SM_API int sm_speckle_filter_u16(sm_handle *h, uint16_t *map, int width, int height, int pitch, int max_size,
+                                 int max_diff, uint8_t *mask, int mask_pitch);
 
 /* u16 SAD volume sad[d][y][x] = zero-padded (2r+1)^2 window sum of the AD plane d, radius <= 7
  * (the volume kernalFindAllSAD / getAllSAD build, Device.cu:67-103 / BlockMatching.cpp:191-261,
