@@ -254,6 +254,46 @@ class BlockMatcher:
             int(max_diff), mask.data_ptr() if mask is not None else None, self._stream_ptr(stream)))
         return map_t
 
+    def set_fill(self, max_gap: int = 0):
+        """The row fill as the matching calls' last step (SM_PARAM_FILL_GAP): with max_gap > 0 every call that
+        returns a map (match, match_lr, match_bgr, match_device, match_subpix[_device], and the group's row bands)
+        ends by filling each run of at most `max_gap` invalid pixels in a row with the smaller of its two
+        neighbours, after the median, the LR check and the speckle filter, on the final left map only.  The mask
+        and the right map stay: mask == 0 and disp != 0 marks the filled pixels.  The default turns it off.  The
+        d-slice and slice-key calls refuse a handle whose gap is not 0."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_FILL_GAP, float(int(max_gap))))
+
+    def fill_invalid(self, map, max_gap: int):  # noqa: A002
+        """The row fill on a host map (sm_fill_invalid_u8 / _u16): a 2-D uint8 or uint16 array in which 0 is
+        invalid.  Returns the filled copy: every run of at most `max_gap` zeros in a row holds min(left, right) of
+        its valid neighbours in that row (whole 16-bit values on a uint16 map), or the one neighbour it has at a
+        border; longer runs, valid pixels and rows without a valid pixel are unchanged."""
+        m = np.array(map, copy=True, order="C")
+        if m.dtype not in (np.uint8, np.uint16) or m.ndim != 2:
+            raise ValueError(f"map: expected a 2-D uint8 or uint16 map, got {m.dtype} {m.shape}")
+        H, W = m.shape
+        fn = self._lib.sm_fill_invalid_u8 if m.dtype == np.uint8 else self._lib.sm_fill_invalid_u16
+        _capi.check(fn(self._h, m.ctypes.data, W, H, W, int(max_gap)))
+        return m
+
+    def fill_invalid_device(self, map_t, max_gap: int, stream=None):
+        """Device form of :meth:`fill_invalid` (sm_fill_invalid_device), in place and async on `stream`: map_t a
+        uint8 or int16 (uint16 bit patterns) cuda tensor [H, W] or [B, H, W] with contiguous rows (row and frame
+        strides are passed on, so a view cut out of a larger tensor works).  Returns map_t."""
+        import torch
+        if map_t.dtype not in (torch.uint8, torch.int16, torch.uint16) or map_t.dim() not in (2, 3) \
+                or not map_t.is_cuda or map_t.stride(-1) != 1:
+            raise ValueError("map_t must be a uint8 or int16 [H, W] or [B, H, W] device tensor with contiguous rows")
+        if map_t.device.index != self.device:
+            raise ValueError(f"the map must be on cuda:{self.device}, the handle's device")
+        B = 1 if map_t.dim() == 2 else map_t.shape[0]
+        H, W = map_t.shape[-2:]
+        fs = map_t.stride(0) if map_t.dim() == 3 else map_t.stride(-2) * H
+        _capi.check(self._lib.sm_fill_invalid_device(
+            self._h, map_t.data_ptr(), map_t.element_size(), W, H, map_t.stride(-2), B, fs, int(max_gap),
+            self._stream_ptr(stream)))
+        return map_t
+
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
                         lr_check: bool = False) -> np.ndarray:
         """The d-slice split of BlockMatcherGroup.match_dslice with `members` members, run one after
@@ -865,6 +905,11 @@ class BlockMatcherGroup:
         calls (match, match_lr) and match_dslice refuse a size > 0 and say why."""
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SPECKLE_SIZE, float(int(size))))
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SPECKLE_RANGE, float(int(range))))
+
+    def set_fill(self, max_gap: int = 0):
+        """BlockMatcher.set_fill on every member: match_batch and the row-band calls (match, match_lr) honour it,
+        since the rule never crosses a row; match_dslice refuses a gap > 0 and says why."""
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_FILL_GAP, float(int(max_gap))))
 
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
               median: bool = False, cost: str = "ad") -> np.ndarray:

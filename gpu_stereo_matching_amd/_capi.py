@@ -37,6 +37,7 @@ SM_PARAM_UNIQUENESS = 7
 SM_PARAM_BOX_WORKGROUPS = 8
 SM_PARAM_SPECKLE_SIZE = 9
 SM_PARAM_SPECKLE_RANGE = 10
+SM_PARAM_FILL_GAP = 11
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (
@@ -58,6 +59,7 @@ EXPORTED = (
     "sm_match_subpix_device", "sm_block_match_subpix_u16", "sm_volume_wta_subpix_device", "sm_reproject_device",
     "sm_reproject_u16",
     "sm_speckle_workspace_bytes", "sm_speckle_filter_device", "sm_speckle_filter_u8", "sm_speckle_filter_u16",
+    "sm_fill_invalid_device", "sm_fill_invalid_u8", "sm_fill_invalid_u16",
 )
 
 
@@ -156,6 +158,9 @@ def load(path: str = LIB_PATH):
     L.sm_speckle_filter_device.argtypes = [vp, vp, i, i, i, i, i, i64, i, i, vp, vp]
     L.sm_speckle_filter_u8.argtypes = [vp, vp, i, i, i, i, i, vp, i]
     L.sm_speckle_filter_u16.argtypes = [vp, vp, i, i, i, i, i, vp, i]
+    L.sm_fill_invalid_device.argtypes = [vp, vp, i, i, i, i, i, i64, i, vp]
+    L.sm_fill_invalid_u8.argtypes = [vp, vp, i, i, i, i]
+    L.sm_fill_invalid_u16.argtypes = [vp, vp, i, i, i, i]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

@@ -231,6 +231,16 @@ hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t st
 template <class T>
 hipError_t launch_speckle(T* map, int W, int H, int pitch, int64_t fstride, int batch, int max_size, int max_diff,
                           uint8_t* mask, uint32_t* label, uint32_t* count, hipStream_t s);
+// row fill (bm_fill.hip), in place on `batch` maps of T = uint8_t or uint16_t (pitch and fstride in elements): every
+// run of at most max_gap invalid (0) pixels in a row takes the smaller of its two valid neighbours in that row, or
+// the one it has at a border; everything else stays.  One launch for the batch, one workgroup per row, no workspace.
+// max_gap 0 launches nothing.  fill_pass_ok: what the launcher takes (the rows of the batch are one grid, and a
+// row's columns are walked in int steps of 4096).
+inline bool fill_pass_ok(int W, int H, int batch) {
+    return W >= 1 && W <= (1 << 30) && H >= 1 && batch >= 1 && (int64_t)H * batch <= 0x7FFFFFFFll;
+}
+template <class T>
+hipError_t launch_fill(T* map, int W, int H, int pitch, int64_t fstride, int batch, int max_gap, hipStream_t s);
 
 hipError_t launch_bgr_to_gray(const uint8_t* src, int W, int H, int pitch, int channels, uint8_t* dst, int dpitch,
                               hipStream_t s);

@@ -1,7 +1,7 @@
 // sm_capi.hip — the C ABI (include/sm_hip.h): handles, parameters, and the matching entry points.
 // (sm_capi_volume.hip: the passes that keep a cost volume; sm_capi_aux.hip: the pre- / post-processing and volume
 // calls; sm_capi_slice.hip: d-slices; sm_capi_group.hip: multi-GPU groups; sm_capi_speckle.hip: the speckle
-// filter; sm_handle.h: what they share.)
+// filter; sm_capi_fill.hip: the row fill; sm_handle.h: what they share.)
 //
 // Replaces blockMatching_gpu (BlockMatching/Device.cu:173-301).  Differences from the
 // reference that are deliberate and documented in DESIGN.md:
@@ -434,13 +434,20 @@ static int run_device(sm_handle* h, const uint8_t* L, const uint8_t* R, int W, i
         const int rc = ws.touch();
         if (rc) return rc;
     }
-    const int rc = run_device_body(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, flags, disp, opitch, ostride,
-                                   right_out, mask_out, apitch, astride);
-    if (rc || h->speckle_size == 0) return rc;
-    // the speckle filter: the last step of every whole-frame matching call, on the final left map and the valid
-    // mask (dense: apitch == W, astride == W * H in every caller); the right map stays as it is
-    if (!sm::speckle_pass_ok(W, H, batch)) return fail(SM_ERR_INVALID_ARG, "speckle filter: frame %dx%d too large", W, H);
-    return run_speckle(ws, h, disp, 1, W, H, opitch, batch, ostride, h->speckle_size, h->speckle_range, mask_out);
+    int rc = run_device_body(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, flags, disp, opitch, ostride,
+                             right_out, mask_out, apitch, astride);
+    if (rc) return rc;
+    if (h->speckle_size != 0) {
+        // the speckle filter: the last step but one of every whole-frame matching call, on the final left map and the
+        // valid mask (dense: apitch == W, astride == W * H in every caller); the right map stays as it is
+        if (!sm::speckle_pass_ok(W, H, batch))
+            return fail(SM_ERR_INVALID_ARG, "speckle filter: frame %dx%d too large", W, H);
+        rc = run_speckle(ws, h, disp, 1, W, H, opitch, batch, ostride, h->speckle_size, h->speckle_range, mask_out);
+        if (rc) return rc;
+    }
+    // the row fill: the last step, on the final left map alone; the mask keeps saying which pixels were measured.
+    // A row band runs it too: rows never interact, so the kept rows get the frame's values
+    return h->fill_gap == 0 ? SM_OK : run_fill(s, disp, 1, W, H, opitch, batch, ostride, h->fill_gap);
 }
 
 int host_match_rows(sm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
@@ -469,11 +476,11 @@ int host_match_rows(sm_handle* h, const uint8_t* left, const uint8_t* right, int
         aux = h->aux.p;
     }
     // zero-copy map: a whole-frame call whose map goes to an sm_host_alloc block and is only written by
-    // the last kernel (no LR check and no speckle filter, which read the left map back)
+    // the last kernel (no LR check, no speckle filter and no row fill, which read the left map back)
     uint8_t* mapped = nullptr;
     static const bool zero_copy = env_switch("SM_ZERO_COPY", true);   // 0 (A/B): device buffer + download always
     if (zero_copy && keep0 == 0 && keep1 == height && !right_out && !mask_out && !(flags & SM_LR_CHECK) &&
-        h->speckle_size == 0)
+        h->speckle_size == 0 && h->fill_gap == 0)
         mapped = host_block_device_ptr(disp_out, (size_t)(height - 1) * out_pitch + width);
     // the start event, like the stage marks, only when the split is recorded (round 4; SM_START_EVENT=1, read
     // once, records it in every call as before, for A/B)
@@ -644,6 +651,14 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         if (!(value >= 0.f) || value > 255.f || (float)v != value)
             return fail(SM_ERR_INVALID_ARG, "speckle range must be an integer in [0, 255] (whole disparities)");
         h->speckle_range = v;
+        return SM_OK;
+    }
+    if (param == SM_PARAM_FILL_GAP) {
+        // (the comparison also rejects NaN; floats above 2^24 are not every integer, and any gap >= the width fills
+        // every run)
+        if (!(value >= 0.f) || value > 16777216.f || (float)(int)value != value)
+            return fail(SM_ERR_INVALID_ARG, "fill gap must be an integer in [0, 2^24] (0 = off)");
+        h->fill_gap = (int)value;
         return SM_OK;
     }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);

@@ -420,6 +420,8 @@ SM_API int sm_group_dslice_block_match_u8(sm_group* g, const uint8_t* left, cons
     for (GroupWorker* w : g->w) {
         rc = speckle_refuse(w->h, "the d-slice group call", "the d-slice calls do not run it");
         if (rc) return rc;
+        rc = fill_refuse(w->h, "the d-slice group call", "the d-slice calls do not run it");
+        if (rc) return rc;
         rc = check_geometry(w->h, width, height, width, radius, num_disp);
         if (rc) return rc;
         rc = check_capacity(w->h, width, height, num_disp);

@@ -187,6 +187,8 @@ SM_API int sm_slice_keys_device(sm_handle* h, const uint8_t* d_left, const uint8
     if (rc) return rc;
     rc = speckle_refuse(h, "a slice-key call", "keys are no map; filter the combined map (sm_speckle_filter_device)");
     if (rc) return rc;
+    rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
+    if (rc) return rc;
     rc = slice_check(d_lo, d_hi);
     if (rc) return rc;
     if (!d_left || !d_right || !d_keys) return fail(SM_ERR_INVALID_ARG, "null device pointer");
@@ -211,6 +213,8 @@ SM_API int sm_guided_slice_keys_device(sm_handle* h, const uint8_t* d_left, cons
     int rc = check_geometry(h, width, height, pitch, radius, d_hi > 0 ? d_hi : 1);
     if (rc) return rc;
     rc = speckle_refuse(h, "a slice-key call", "keys are no map; filter the combined map (sm_speckle_filter_device)");
+    if (rc) return rc;
+    rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
     if (rc) return rc;
     rc = guided_radius_check(radius);
     if (rc) return rc;
@@ -240,6 +244,8 @@ SM_API int sm_slice_keys_lr_device(sm_handle* h, const uint8_t* d_left, const ui
     int rc = check_geometry(h, width, height, pitch, radius, d_hi > 0 ? d_hi : 1);
     if (rc) return rc;
     rc = speckle_refuse(h, "a slice-key call", "keys are no map; filter the combined map (sm_speckle_filter_device)");
+    if (rc) return rc;
+    rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
     if (rc) return rc;
     if (flags & SM_AGG_SGM)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: SM_AGG_SGM's recursion over d crosses the slices");
@@ -296,6 +302,8 @@ SM_API int sm_dslice_rehearse_u8(sm_handle* h, const uint8_t* left, const uint8_
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
     if (members < 1 || members > 64) return fail(SM_ERR_INVALID_ARG, "members %d out of [1, 64]", members);
     rc = speckle_refuse(h, "the d-slice rehearsal", "the d-slice calls do not run it");
+    if (rc) return rc;
+    rc = fill_refuse(h, "the d-slice rehearsal", "the d-slice calls do not run it");
     if (rc) return rc;
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
     const DsliceCfg cfg{width, height, radius, num_disp, guided, (flags & SM_LR_CHECK) != 0};

@@ -158,12 +158,18 @@ VolumeOut subpix_out(uint16_t* disp16, int pitch, int64_t stride, uint16_t* righ
 }
 
 // The handle's speckle filter as the sub-pixel calls' last step: on the 1/16-px left map and the mask, regions
-// joined within 16 * range, as StereoSGBM's speckleRange on its 1/16-px map
+// joined within 16 * range, as StereoSGBM's speckleRange on its 1/16-px map; and after it the handle's row fill, on
+// the 1/16-px left map alone (whole 16-bit values)
 int subpix_speckle(WsScope& ws, sm_handle* h, uint16_t* disp16, int W, int H, int pitch, int batch, int64_t stride,
                    uint8_t* mask) {
-    if (h->speckle_size == 0) return SM_OK;
-    if (!sm::speckle_pass_ok(W, H, batch)) return fail(SM_ERR_INVALID_ARG, "speckle filter: frame %dx%d too large", W, H);
-    return run_speckle(ws, h, disp16, 2, W, H, pitch, batch, stride, h->speckle_size, 16 * h->speckle_range, mask);
+    if (h->speckle_size != 0) {
+        if (!sm::speckle_pass_ok(W, H, batch))
+            return fail(SM_ERR_INVALID_ARG, "speckle filter: frame %dx%d too large", W, H);
+        const int rc = run_speckle(ws, h, disp16, 2, W, H, pitch, batch, stride, h->speckle_size,
+                                   16 * h->speckle_range, mask);
+        if (rc) return rc;
+    }
+    return h->fill_gap == 0 ? SM_OK : run_fill(ws.stream(), disp16, 2, W, H, pitch, batch, stride, h->fill_gap);
 }
 
 }  // namespace

@@ -121,6 +121,7 @@ struct sm_handle {
     int uniqueness = 0;          // SM_PARAM_UNIQUENESS: 0 off, 1..99 the sub-pixel calls' uniqueness ratio
     int speckle_size = 0;        // SM_PARAM_SPECKLE_SIZE: 0 off, else the largest region the matching calls remove
     int speckle_range = 1;       // SM_PARAM_SPECKLE_RANGE: whole disparities joined into one region, 0..255
+    int fill_gap = 0;            // SM_PARAM_FILL_GAP: 0 off, else the longest run of a row the matching calls fill
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -214,6 +215,16 @@ inline int speckle_refuse(const sm_handle* h, const char* call, const char* why)
 // `spk` workspace (sm_capi_speckle.hip).  The arguments have been checked.
 int run_speckle(WsScope& ws, sm_handle* h, void* map, int elem_bytes, int W, int H, int pitch, int batch,
                 int64_t fstride, int max_size, int max_diff, uint8_t* mask);
+// The same for the row fill (SM_PARAM_FILL_GAP): a call whose result is no map, or that does not run the steps the
+// fill comes after
+inline int fill_refuse(const sm_handle* h, const char* call, const char* why) {
+    if (!h || h->fill_gap == 0) return SM_OK;
+    return fail(SM_ERR_INVALID_ARG, "%s cannot honour the row fill (SM_PARAM_FILL_GAP %d): %s", call, h->fill_gap, why);
+}
+// The row fill (bm_fill.hip) in place on `batch` device maps of elem_bytes 1 or 2, on stream s; it takes no
+// workspace, so it joins no WsScope (sm_capi_fill.hip).  The arguments have been checked, except the frame
+// against fill_pass_ok.
+int run_fill(hipStream_t s, void* map, int elem_bytes, int W, int H, int pitch, int batch, int64_t fstride, int max_gap);
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out);
 
 // SM_AGG_GUIDED's radii (bm_guided_plan.h): every guided entry rejects the others before it takes a workspace

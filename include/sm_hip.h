@@ -148,9 +148,15 @@ enum {
                                   (sm_speckle_filter_device) on its final left map, after the median and the LR
                                   check: regions of at most this many pixels become 0.  See "speckle filter" below
                                   for the calls that honour it and those that refuse it */
-    SM_PARAM_SPECKLE_RANGE = 10 /* StereoSGBM's speckleRange: whole disparities, an integer 0..255, default 1.  The
+    SM_PARAM_SPECKLE_RANGE = 10, /* StereoSGBM's speckleRange: whole disparities, an integer 0..255, default 1.  The
                                   8-bit matching calls join neighbours with |a - b| <= range, the 1/16-px calls with
                                   |a - b| <= 16 * range, as StereoSGBM does on its 1/16-px map */
+    SM_PARAM_FILL_GAP = 11     /* the row fill's max_gap: an integer 0 .. 2^24, 0 (default) = off.  With a gap > 0
+                                  every matching call that returns a map ends with the row fill
+                                  (sm_fill_invalid_device) on its final left map, after the median, the LR check and
+                                  the speckle filter: runs of at most this many invalid pixels in a row take the
+                                  smaller of their two neighbours.  Other values: SM_ERR_INVALID_ARG.  See "row fill"
+                                  below for the calls that honour it and those that refuse it */
 };
 
 typedef struct sm_handle sm_handle;
@@ -412,6 +418,46 @@ SM_API int sm_speckle_filter_u8(sm_handle *h, uint8_t *map, int width, int heigh
                                 int max_diff, uint8_t *mask, int mask_pitch);
 SM_API int sm_speckle_filter_u16(sm_handle *h, uint16_t *map, int width, int height, int pitch, int max_size,
                                  int max_diff, uint8_t *mask, int mask_pitch);
+
+/* ---- row fill: invalidated disparities closed from their neighbours along the row (this build's extension) ----
+ * The last step of a classical SGM pipeline, on a uint8 map or a uint16 (1/16 px) map in which 0 is this library's
+ * invalid value.  The LR check and the speckle filter set 0 wherever they distrust a pixel; this step sets a value
+ * back.  All integer, in place:
+ *   a pixel is valid iff its value is != 0; valid pixels are never changed;
+ *   a run is a maximal stretch of invalid pixels in one row, columns a .. b inside [0, width); its left neighbour is
+ *     the pixel at a - 1 if a > 0, its right neighbour the pixel at b + 1 if b < width - 1; rows never interact;
+ *   a run longer than max_gap (b - a + 1 > max_gap) stays as it is; otherwise every pixel of the run becomes
+ *     min(left, right) when both neighbours exist, and the one neighbour's value when the run touches a border; a
+ *     row with no valid pixel stays 0;
+ *   the minimum is taken on the whole element: on a uint16 map 0x00FF against 0x0100 gives 0x00FF;
+ *   max_gap = 0 fills nothing (no launch); any max_gap >= width fills every run; the range is 0 .. 2^24;
+ *   the bytes between width and pitch are neither read as neighbours nor written.
+ * Why the smaller value: it is the farther surface, and the pixels the check removes next to a depth edge are the
+ * ones the nearer object hides in the other view, so what is seen there is the background.
+ * Neighbours are valid pixels of the input, so the result does not depend on the order in which runs are filled.
+ * A mask plane is not touched: after an LR-checked call, mask == 0 && disp != 0 marks exactly the filled pixels.
+ * The map does not say which of its values were measured and which interpolated; a caller who needs the
+ * distinction keeps the mask.
+ * sm_fill_invalid_device: in place on `batch` device maps of elem_bytes 1 (uint8) or 2 (uint16), pitch and
+ * frame_stride in elements; asynchronous on `stream`; one launch for the batch, no workspace.  Every argument is
+ * checked before the device is touched: elem_bytes, the frame size, batch >= 1, pitch >= width, 0 <= max_gap <=
+ * 2^24, the map pointer, the handle's capacity.
+ * sm_fill_invalid_u8 / _u16: the same on one host frame (pitch in elements), synchronous.
+ * With SM_PARAM_FILL_GAP > 0 the fill is the last step, after the median, the LR check and the speckle filter, of
+ * sm_block_match_u8, sm_block_match_lr_u8 (the right map and the valid mask stay as they are),
+ * sm_block_match_bgr_u8, sm_match_device and sm_group_block_match_batch_u8 for every aggregation and flag, and of
+ * sm_match_subpix_device / sm_block_match_subpix_u16 on the 1/16-px left map.  The row-band group calls honour it
+ * too: the rule never crosses a row, so a band's kept rows get exactly the frame's values (with the speckle filter
+ * set as well, that filter's refusal comes first).  A map the caller receives into an sm_host_alloc block is then
+ * written to a device buffer and downloaded, not written straight over PCIe: the fill reads the map back.  Calls
+ * that cannot honour it return SM_ERR_INVALID_ARG, with a message naming the row fill, before any device work:
+ * sm_group_dslice_block_match_u8 and sm_dslice_rehearse_u8 (the d-slice calls do not run the steps it comes
+ * after), and the slice-key calls (sm_slice_keys_device, sm_guided_slice_keys_device, sm_slice_keys_lr_device:
+ * keys are no map).  The segment-tree calls do not apply it, as with the speckle filter. */
+SM_API int sm_fill_invalid_device(sm_handle *h, void *d_map, int elem_bytes, int width, int height, int pitch,
+                                  int batch, int64_t frame_stride, int max_gap, void *stream);
+SM_API int sm_fill_invalid_u8(sm_handle *h, uint8_t *map, int width, int height, int pitch, int max_gap);
+SM_API int sm_fill_invalid_u16(sm_handle *h, uint16_t *map, int width, int height, int pitch, int max_gap);
 
 /* u16 SAD volume sad[d][y][x] = zero-padded (2r+1)^2 window sum of the AD plane d, radius <= 7
  * (the volume kernalFindAllSAD / getAllSAD build, Device.cu:67-103 / BlockMatching.cpp:191-261,
