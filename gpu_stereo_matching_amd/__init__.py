@@ -206,6 +206,12 @@ class BlockMatcher:
         tile per workgroup.  Same maps and keys at every n; the VALU kernels ignore it."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_WORKGROUPS, float(n)))
 
+    def set_box_queue_workgroups(self, n=0):
+        """Workgroups of a matrix-pipe box launch that draws its tiles from a queue (SM_PARAM_BOX_QUEUE_WORKGROUPS,
+        with set_box_workgroups(0)): 0 auto, one per resident slot where the launch is large enough, n >= 1 that many
+        at any launch size, also more than there are tiles.  Same maps and keys at every n."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_BOX_QUEUE_WORKGROUPS, float(n)))
+
     def set_speckle(self, size: int = 0, range: int = 1):  # noqa: A002  (StereoSGBM's name)
         """StereoSGBM's speckleWindowSize / speckleRange (SM_PARAM_SPECKLE_SIZE / _RANGE): with size > 0 the
         whole-frame matching calls (match, match_lr, match_bgr, match_device, match_subpix[_device]) end with the

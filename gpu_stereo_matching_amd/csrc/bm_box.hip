@@ -611,7 +611,7 @@ hipError_t launch_left(const MatchArgs& a, int64_t blocks, int tiles_x, int tile
 // kernel the left-only pass takes is box_tile_kernel's (bm_box_plan.h)
 template <int R, int DMAX, bool RIGHT>
 hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel,
-                     int box_workgroups = 0) {
+                     int box_workgroups = 0, uint32_t* box_queue = nullptr, int box_queue_wgs = 0) {
     using G = Geo<R, DMAX, kWavesD<RIGHT, R, DMAX>>;
     const int tiles_x = (a.W + G::TW - 1) / G::TW;
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
@@ -633,7 +633,8 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
         const BoxTileKernel k = box_tile_kernel(R, a.d_hi - a.d_lo, blocks, device_cus(), box_kernel,
                                                 box_mfma_scope(box_geom(a, batch), a.valid_mode));
         switch (k) {
-            case BoxTileKernel::Matrix: return launch_box_match_mfma(a, batch, s, box_workgroups);
+            case BoxTileKernel::Matrix:
+                return launch_box_match_mfma(a, batch, s, box_workgroups, box_queue, box_queue_wgs);
             case BoxTileKernel::Wide16:
             case BoxTileKernel::Mid8:
                 if constexpr (kWideR<R>) {
@@ -650,14 +651,15 @@ hipError_t launch_rd(const MatchArgs& a, int batch, const RightOut* ro, hipStrea
 
 template <int R, bool RIGHT>
 hipError_t launch_r(const MatchArgs& a, int batch, const RightOut* ro, hipStream_t s, int box_kernel = 0,
-                    int box_workgroups = 0) {
+                    int box_workgroups = 0, uint32_t* box_queue = nullptr, int box_queue_wgs = 0) {
     const int dmax = box_dmax(a.d_hi - a.d_lo);
-    if (dmax == 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
-    if (dmax == 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    const int bk = box_kernel, bw = box_workgroups;
+    if (dmax == 64) return launch_rd<R, 64, RIGHT>(a, batch, ro, s, bk, bw, box_queue, box_queue_wgs);
+    if (dmax == 128) return launch_rd<R, 128, RIGHT>(a, batch, ro, s, bk, bw, box_queue, box_queue_wgs);
     // 192 (cfg5): the right band and the right-key rows sized for 192, not 256, keep the plain kernel
     // at 4 workgroups/CU and the right-view kernel at 2
-    if (dmax == 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
-    return launch_rd<R, 256, RIGHT>(a, batch, ro, s, box_kernel, box_workgroups);
+    if (dmax == 192) return launch_rd<R, 192, RIGHT>(a, batch, ro, s, bk, bw, box_queue, box_queue_wgs);
+    return launch_rd<R, 256, RIGHT>(a, batch, ro, s, bk, bw, box_queue, box_queue_wgs);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -701,9 +703,11 @@ __global__ __launch_bounds__(256) void box_match_generic_kernel(MatchArgs a, int
 
 }  // namespace
 
-hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel, int box_workgroups) {
+hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel, int box_workgroups,
+                            uint32_t* box_queue, int box_queue_wgs) {
     return with_radius<0, kMaxBoxRadius>(a.radius, hipErrorInvalidValue, [&](auto r) {
-        return launch_r<decltype(r)::value, false>(a, batch, nullptr, s, box_kernel, box_workgroups);
+        return launch_r<decltype(r)::value, false>(a, batch, nullptr, s, box_kernel, box_workgroups, box_queue,
+                                                   box_queue_wgs);
     });
 }
 

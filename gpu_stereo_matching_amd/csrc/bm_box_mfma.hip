@@ -1,5 +1,5 @@
 // bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
-// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22, §24).
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22, §24, §30).
 //
 // Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
 //
@@ -10,10 +10,11 @@
 // tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
 // A workgroup walks a contiguous range of tiles; along a row of tiles it keeps the right band in LDS and stages
-// only the new columns.  The paired loop is written slot by slot, every MFMA between vector work of
-// its own wave (run_paired), and carries its key constants and R addresses from pass to pass (DESIGN
-// §26); a wave's masked passes are the same body plus the mask work, continuing where its unmasked passes end
-// (DESIGN §27).  run() is the loop of the one-d-per-pass kernels alone.
+// only the new columns.  Large launches run one workgroup per resident slot, each drawing one run of
+// tiles after another from a counter (box_mfma_queue_kernel).  The paired loop is written slot by slot,
+// every MFMA between vector work of its own wave (run_paired), and carries its key constants and R
+// addresses from pass to pass; a wave's masked passes are the same body plus the mask work, continuing
+// where its unmasked passes end.  run() is the loop of the one-d-per-pass kernels alone.
 //
 // Exactness: every number is an integer its format holds exactly.
 //   staging   L, R as f16 0x6400 | v = 1024 + v (unit spacing on [1024, 2048)): L' - R' == L - R exactly,
@@ -54,6 +55,7 @@ constexpr int kNW = 4;          // waves per workgroup, one per SIMD
 constexpr int kThreads = 64 * kNW;
 constexpr int kColB = 128;      // bytes per staged column (64 rows of f16)
 constexpr uint32_t kInfBits = 0x7F800000u;
+constexpr int kQueueLdsBytes = 16;   // behind a queue launch's staged tiles: the LDS word of the grab index
 
 // NP: disparities per loop pass.  2: the paired loop on 48-row tiles.  1: one d per pass on 64 - 2R rows, for short
 // d ranges at small radii, where a tile's staging and fold outweigh its loop and fewer, larger tiles win
@@ -169,9 +171,12 @@ __device__ __forceinline__ f4 mfma(u4 a, u4 b, f4 c) {
 }
 
 // WALK: the workgroup walks a range of tiles; false: one tile per workgroup, the tile loop and everything carried
-// compiled away
-template <int R, int DMAX, int NP, bool WALK>
-__device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, int tiles_y, int per, int rem) {
+// compiled away.  QUEUE (with WALK): the workgroup walks one run of tiles after another, box_queue_grab of what the
+// launch's grab counter `queue`, zero at the launch, hands it; per is then the launch's tile count.  The
+// kernels of static ranges are compiled without any of it
+template <int R, int DMAX, int NP, bool WALK, bool QUEUE>
+__device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, int tiles_y, int per, int rem,
+                                               uint32_t* queue) {
     using G = MG<R, DMAX, NP>;
     constexpr int NXB = G::NXB, NOB = G::NOB;
     // (aligned to 16 columns, the period of slot()'s swizzle in the address)
@@ -188,13 +193,30 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
     // Workgroup position k of n walks the tiles [k T / n, (k + 1) T / n) of the sequence [frame][ty][tx]: with n = T
     // one tile each; with fewer, runs along a row of tiles, whose right bands overlap.  T = per n + rem from the
     // host, so k T / n = k per + k rem / n, and the 64-bit division is skipped where n divides T
-    const int wg = xcd_tile(blockIdx.x, gridDim.x);
+    static_assert(!QUEUE || WALK, "a queue workgroup walks its runs");
+    constexpr bool queued = QUEUE;
+    const int wg = queued ? 0 : xcd_tile(blockIdx.x, gridDim.x);
     int t_begin = wg * per, t_end = t_begin + per;
     if (WALK && rem != 0) {
         t_begin += (int)((int64_t)wg * rem / (int)gridDim.x);
         t_end += (int)((int64_t)(wg + 1) * rem / (int)gridDim.x);
     }
     if constexpr (!WALK) t_end = t_begin + 1;
+    // The queue: lane 0 of wave 0 draws, the grab index reaches the other waves through one LDS word behind the
+    // staged tiles, which neither they nor the fold plane alias.  The word is written between a tile's first barrier
+    // and the barrier after its disparity loops, and read after that one or, here, after a barrier of its own
+    uint32_t* const qword = reinterpret_cast<uint32_t*>(smem + G::LDS_BYTES);
+    auto take_run = [&] {
+        const uint32_t gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)*qword);
+        const BoxGrab run = box_queue_grab(gi, (uint32_t)per, (uint32_t)tiles_x, gridDim.x);
+        t_begin = (int)run.begin;
+        t_end = (int)run.end;
+    };
+    if constexpr (queued) {
+        if (tid == 0) *qword = atomicAdd(queue, 1u);
+        __syncthreads();
+        take_run();
+    }
     if (t_begin >= t_end) return;
     const int tiles = tiles_x * tiles_y;
     int frame = t_begin / tiles;
@@ -299,6 +321,14 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         if constexpr (NP == 1) issue_prefetch();
 
         __syncthreads();
+
+        // The run's last tile: the grab for the next run goes out now, its latency under the disparity loops, and
+        // into the LDS word behind them, ahead of the barrier every wave passes before it reads the word
+        uint32_t next_grab = 0;
+        const bool draw = queued && tile + 1 == t_end && tid == 0;
+        if constexpr (queued) {
+            if (draw) next_grab = atomicAdd(queue, 1u);
+        }
 
         // One loop over [lo, hi) in the compiler's order; MASKED: with the c >= d and c < W mask of the staged columns
         // and the d <= W - x mask of the outputs.  The NP = 1 kernels run it for both parts of a wave's range; the
@@ -670,6 +700,9 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             run(std::false_type{}, dw_lo, dw_m);
             run(std::true_type{}, dw_m, dw_hi);
         }
+        if constexpr (queued) {
+            if (draw) *qword = next_grab;
+        }
 
         __syncthreads();   // every wave is done with the staged tiles: the fold plane aliases them
 
@@ -712,14 +745,24 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             }
         }
 
-        // ---- the next tile of the range ----
-        if (tile + 1 == t_end) break;
-        carried = carry_next;
-        if (++tx == tiles_x) {
-            tx = 0;
-            if (++ty == tiles_y) {
-                ty = 0;
-                ++frame;
+        // ---- the next tile of the range, or the first of the next run ----
+        if (tile + 1 == t_end) {
+            if constexpr (!queued) break;
+            take_run();
+            if (t_begin >= t_end) break;
+            tile = t_begin - 1;
+            frame = t_begin / tiles;
+            ty = (t_begin - frame * tiles) / tiles_x;
+            tx = t_begin - frame * tiles - ty * tiles_x;
+            carried = false;
+        } else {
+            carried = carry_next;
+            if (++tx == tiles_x) {
+                tx = 0;
+                if (++ty == tiles_y) {
+                    ty = 0;
+                    ++frame;
+                }
             }
         }
         if (!carried) {
@@ -756,28 +799,42 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
 template <int R, int DMAX, int NP>
 __global__ __launch_bounds__(kThreads, 3) void box_mfma_kernel(MatchArgs a, int tiles_x, int tiles_y, int per,
                                                                 int rem) {
-    box_mfma_tiles<R, DMAX, NP, true>(a, tiles_x, tiles_y, per, rem);
+    box_mfma_tiles<R, DMAX, NP, true, false>(a, tiles_x, tiles_y, per, rem, nullptr);
+}
+
+// The paired loop's workgroups drawing runs of `total` tiles from the counter `queue`
+template <int R, int DMAX>
+__global__ __launch_bounds__(kThreads, 3) void box_mfma_queue_kernel(MatchArgs a, int tiles_x, int tiles_y, int total,
+                                                                      uint32_t* queue) {
+    box_mfma_tiles<R, DMAX, 2, true, true>(a, tiles_x, tiles_y, total, 0, queue);
 }
 
 // One d per pass, one tile per workgroup (what auto launches at NP = 1): with the tile loop around it the NP = 1
 // disparity loop loses the scheduler's order (42 s_nop per pass instead of 4) whatever its register count
 template <int R, int DMAX>
 __global__ __launch_bounds__(kThreads, 3) void box_mfma_tile_kernel(MatchArgs a, int tiles_x, int tiles_y) {
-    box_mfma_tiles<R, DMAX, 1, false>(a, tiles_x, tiles_y, 1, 0);
+    box_mfma_tiles<R, DMAX, 1, false, false>(a, tiles_x, tiles_y, 1, 0, nullptr);
 }
 
-// Workgroups launched per resident slot in auto mode.  One per slot is the slowest form (1080p D = 128 r = 5 x 128
-// frames: 5.40 ms against 5.07 for one tile per workgroup): the three waves of a SIMD keep their age order for the
-// whole launch and the launch ends with the youngest.  Shorter ranges let the dispatcher even that out: 2 / 4 / 8 / 16
-// per slot 5.14 / 4.94 / 4.98 / 4.94 ms, D = 256 x 32 frames 2.48 / 2.42 / 2.39 / 2.39
-// (profiles/microbench/box_mfma_rows_ab.txt)
+// Static ranges launched per resident slot in auto mode, where the launch does not draw from the queue (no counter
+// from the caller, or box_queue_workgroups says no: few tiles per slot).  One static range per slot is the slowest form
+// (1080p D = 128 r = 5 x 128 frames: 5.40 ms against 5.07 for one tile per workgroup): the three waves of a SIMD keep
+// their age order for the whole launch, equal shares go to workgroups that do not run at equal speed, and the launch
+// ends with the youngest.  Shorter ranges let the dispatcher even that out: 2 / 4 / 8 / 16 per slot 5.14 / 4.94 / 4.98 /
+// 4.94 ms, D = 256 x 32 frames 2.48 / 2.42 / 2.39 / 2.39 (profiles/microbench/box_mfma_rows_ab.txt).  The queue is the
+// other cure: one workgroup per slot, each taking what it has time for
 constexpr int kRangesPerSlot = 16;
 
-// workgroups: 0 auto (kRangesPerSlot ranges of tiles per resident workgroup slot), n >= 1 that many, at most one
-// per tile
+// workgroups: 0 auto, n >= 1 that many static ranges, at most one per tile.  Auto: with a counter from the caller,
+// box_queue_workgroups(.., queue_workgroups) workgroups that draw their tiles from it, else kRangesPerSlot static
+// ranges of tiles per resident workgroup slot
 template <int R, int DMAX, int NP>
-hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
+hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgroups, uint32_t* queue,
+                      int queue_workgroups) {
     using G = MG<R, DMAX, NP>;
+    static_assert(NP == box_mfma_np(R, NP == 1 ? 32 : DMAX) && G::TOX == box_mfma_tox(R, NP) &&
+                      G::TOY == box_mfma_toy(R, NP),
+                  "bm_box_plan.h states this tile");
     const int tiles_x = (a.W + G::TOX - 1) / G::TOX;
     const int tiles_y = (a.H + G::TOY - 1) / G::TOY;
     const int64_t total = (int64_t)tiles_x * tiles_y * batch;
@@ -790,6 +847,23 @@ hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgrou
             hipLaunchKernelGGL((box_mfma_tile_kernel<R, DMAX>), dim3((unsigned)total), dim3(kThreads),
                                (size_t)G::LDS_BYTES, s, a, tiles_x, tiles_y);
             return hipGetLastError();
+        }
+    }
+    if constexpr (NP == 2) {
+        if (n == 0 && queue) {
+            int slots = 0;
+            hipError_t e = resident_workgroups(reinterpret_cast<const void*>(&box_mfma_queue_kernel<R, DMAX>), kThreads,
+                                               (size_t)G::LDS_BYTES + kQueueLdsBytes, &slots);
+            if (e != hipSuccess) return e;
+            const int q = box_queue_workgroups(NP, a.d_hi - a.d_lo, total, slots, workgroups, queue_workgroups);
+            if (q > 0) {
+                // the counter is zeroed on the launch's stream, so launches of one handle follow each other on it
+                e = hipMemsetAsync(queue, 0, sizeof(uint32_t), s);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL((box_mfma_queue_kernel<R, DMAX>), dim3((unsigned)q), dim3(kThreads),
+                                   (size_t)G::LDS_BYTES + kQueueLdsBytes, s, a, tiles_x, tiles_y, (int)total, queue);
+                return hipGetLastError();
+            }
         }
     }
     if (n == 0) {
@@ -806,31 +880,35 @@ hipError_t launch_rdp(const MatchArgs& a, int batch, hipStream_t s, int workgrou
 }
 
 template <int R, int DMAX>
-hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
+hipError_t launch_rd(const MatchArgs& a, int batch, hipStream_t s, int workgroups, uint32_t* queue,
+                     int queue_workgroups) {
     // short ranges at r <= 2 keep one d per pass on 62- / 60-row tiles: 1080p x 32 frames, D = 8 r = 1 0.206 against
     // 0.221 ms, D = 32 r = 2 0.396 against 0.404; from r = 3 or D = 48 on the paired loop is level or ahead
     // (profiles/microbench/box_mfma_pairs_ab.txt)
     if constexpr (DMAX == 64 && R <= 2) {
-        if (a.d_hi - a.d_lo <= 32) return launch_rdp<R, DMAX, 1>(a, batch, s, workgroups);
+        if (a.d_hi - a.d_lo <= 32) return launch_rdp<R, DMAX, 1>(a, batch, s, workgroups, queue, queue_workgroups);
     }
-    return launch_rdp<R, DMAX, 2>(a, batch, s, workgroups);
+    return launch_rdp<R, DMAX, 2>(a, batch, s, workgroups, queue, queue_workgroups);
 }
 
 template <int R>
-hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
+hipError_t launch_r(const MatchArgs& a, int batch, hipStream_t s, int workgroups, uint32_t* queue,
+                    int queue_workgroups) {
     const int dspan = a.d_hi - a.d_lo;
-    if (dspan <= 64) return launch_rd<R, 64>(a, batch, s, workgroups);
-    if (dspan <= 128) return launch_rd<R, 128>(a, batch, s, workgroups);
-    if (dspan <= 192) return launch_rd<R, 192>(a, batch, s, workgroups);
-    return launch_rd<R, 256>(a, batch, s, workgroups);
+    if (dspan <= 64) return launch_rd<R, 64>(a, batch, s, workgroups, queue, queue_workgroups);
+    if (dspan <= 128) return launch_rd<R, 128>(a, batch, s, workgroups, queue, queue_workgroups);
+    if (dspan <= 192) return launch_rd<R, 192>(a, batch, s, workgroups, queue, queue_workgroups);
+    return launch_rd<R, 256>(a, batch, s, workgroups, queue, queue_workgroups);
 }
 
 }  // namespace
 
-hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups) {
+hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups, uint32_t* queue,
+                                 int queue_workgroups) {
     if (!box_mfma_scope(box_geom(a, batch), a.valid_mode)) return hipErrorInvalidValue;
-    return with_radius<1, kMaxFastRadius>(a.radius, hipErrorInvalidValue,
-                                          [&](auto r) { return launch_r<decltype(r)::value>(a, batch, s, workgroups); });
+    return with_radius<1, kMaxFastRadius>(a.radius, hipErrorInvalidValue, [&](auto r) {
+        return launch_r<decltype(r)::value>(a, batch, s, workgroups, queue, queue_workgroups);
+    });
 }
 
 }  // namespace sm

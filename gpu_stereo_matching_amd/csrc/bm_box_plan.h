@@ -118,6 +118,108 @@ constexpr BoxTileKernel box_tile_kernel(int radius, int dspan, int64_t tiles, in
     return BoxTileKernel::Plain;
 }
 
+// ---- the matrix-pipe kernel's tiles and how its workgroups come by them (bm_box_mfma.hip ties MG to these) ----
+// disparities per loop pass: one for spans of at most 32 at r <= 2, else two (launch_rd there)
+constexpr int box_mfma_np(int radius, int dspan) { return dspan <= 32 && radius <= 2 ? 1 : 2; }
+// output columns and rows of a tile
+constexpr int box_mfma_tox(int radius, int np) { return np == 1 || radius <= 6 ? 64 - 2 * radius : 48; }
+constexpr int box_mfma_toy(int radius, int np) { return np == 2 ? 48 : 64 - 2 * radius; }
+constexpr int64_t box_mfma_tiles(int W, int H, int radius, int dspan, int batch) {
+    const int np = box_mfma_np(radius, dspan), tox = box_mfma_tox(radius, np), toy = box_mfma_toy(radius, np);
+    return (int64_t)((W + tox - 1) / tox) * ((H + toy - 1) / toy) * batch;
+}
+
+#if defined(__HIPCC__)
+#define SM_PLAN_HD __host__ __device__
+#else
+#define SM_PLAN_HD
+#endif
+
+// Self-scheduled launches: the workgroups of a launch draw runs of tiles from one counter, grab g
+// being the g-th value the counter hands out.  box_queue_grab maps g to its half-open range of the sequence
+// [frame][ty][tx]; a workgroup walks the range like a static one (a fresh band at its first tile and at every row
+// start, carried bands between).  The schedule is a sequence of levels of equal grabs whose size halves from level
+// to level: s0 = kQueueRows rows of tiles, then s0 / 2, s0 / 4, .. 1.  The level of size s hands out whole grabs
+// while more than kQueueTail * slots of them remain, so about that many grabs of size s per slot, which is twice as
+// many of the next size, are left when the size halves; the last level hands out every remaining tile singly.  So
+// sizes never increase, every tile has one owner, the launch ends with single tiles (the slots end within about a
+// tile of each other), and a launch with few tiles per slot starts at the level that fits it.  At most 16 levels
+// (s0 <= 32768), one 32-bit division each; a grab past the last is empty.
+constexpr uint32_t kQueueRows = 1;
+constexpr uint32_t kQueueTail = 1;
+struct BoxGrab {
+    uint32_t begin, end;
+};
+SM_PLAN_HD inline BoxGrab box_queue_grab(uint32_t g, uint32_t total, uint32_t tiles_x, uint32_t slots) {
+    uint32_t s = tiles_x * kQueueRows;
+    if (s > 32768u) s = 32768u;
+    uint32_t t = 0;   // the first tile of the level
+    for (; s > 1; s >>= 1) {
+        const uint32_t q = (total - t) / s, keep = slots * kQueueTail;
+        if (q <= keep) continue;
+        const uint32_t n = q - keep;
+        if (g < n) return BoxGrab{t + g * s, t + g * s + s};
+        g -= n;
+        t += n * s;
+    }
+    return g < total - t ? BoxGrab{t + g, t + g + 1} : BoxGrab{total, total};
+}
+// the grabs that are not empty (the counter ends at this plus one empty grab per workgroup)
+inline uint32_t box_queue_grabs(uint32_t total, uint32_t tiles_x, uint32_t slots) {
+    uint32_t s = tiles_x * kQueueRows, t = 0, grabs = 0;
+    if (s > 32768u) s = 32768u;
+    for (; s > 1; s >>= 1) {
+        const uint32_t q = (total - t) / s, keep = slots * kQueueTail;
+        if (q <= keep) continue;
+        grabs += q - keep;
+        t += (q - keep) * s;
+    }
+    return grabs + (total - t);
+}
+
+// Whether a matrix-pipe launch of `tiles` tiles over dspan disparities draws them from the queue, and with how many
+// workgroups (0: it keeps static ranges).  workgroups: SM_PARAM_BOX_WORKGROUPS, queue_workgroups:
+// SM_PARAM_BOX_QUEUE_WORKGROUPS, slots: the workgroups the device holds at once.  An explicit range count keeps the
+// static ranges, one d per pass keeps its one-tile kernel, an explicit queue size is taken as it is (a test frame of a
+// dozen tiles), and auto takes one workgroup per slot where a slot has enough tiles to draw, by what was measured
+// against the static ranges, ms per launch (profiles/microbench/box_mfma_queue_ab.txt):
+//   138 tiles per slot   1080p D = 128 r = 5 x 128 frames 4.71 -> 4.47: the queue
+//   30..38 per slot      1080p x 32 frames at r = 5, D = 8 / 16 / 32 / 64: 0.253 -> 0.233, 0.311 -> 0.286, 0.436 ->
+//                        0.402, 0.689 -> 0.651: the queue, for spans up to kQueueShortSpan, whose tiles are mostly
+//                        staging, which a carried band saves.  Longer spans are mixed at this size (D = 128 r = 1 / 5 /
+//                        7 and D = 256 gain 1.2 / 3.1 / 2.2 / 1.7 %, D = 128 r = 3 and 4K D = 192 x 8 frames lose 0.7 /
+//                        1.6 %, and the tile count does not tell them apart): static ranges
+//   4..9 per slot        headline x 4 frames, 463 x 370 D = 64 x 96: 0.166 -> 0.189, 0.185 -> 0.190, 0.187 -> 0.200:
+//                        static ranges (a run is one or two tiles however they are handed out)
+constexpr int kQueueMinTilesPerSlot = 64, kQueueMinTilesPerSlotShort = 28, kQueueShortSpan = 64;
+constexpr int kMaxQueueWorkgroups = 1 << 20;
+constexpr int box_queue_workgroups(int np, int dspan, int64_t tiles, int slots, int workgroups,
+                                   int queue_workgroups) {
+    if (np != 2 || workgroups != 0 || slots < 1 || queue_workgroups < 0 || queue_workgroups > kMaxQueueWorkgroups)
+        return 0;
+    if (queue_workgroups > 0) return queue_workgroups;
+    const int per_slot = dspan <= kQueueShortSpan ? kQueueMinTilesPerSlotShort : kQueueMinTilesPerSlot;
+    return tiles >= (int64_t)per_slot * slots ? slots : 0;
+}
+
+// Whether the runner takes the handle's grab counter for a left-only tile pass: the pass launches the matrix-pipe
+// kernel (box_tile_kernel on the VALU kernels' tile count, as launch_rd in bm_box.hip asks it) and
+// box_queue_workgroups says it draws from the queue, with the slots the kernel has on every device so far:
+// kBoxMfmaWorkgroupsPerCu per CU (its launch bounds; 24 to 48 KB of LDS each).  A pass that keeps static ranges
+// takes no workspace, so it joins no ordering and records no event.  The launcher asks again with the slots the
+// occupancy query gives it
+constexpr int kBoxMfmaWorkgroupsPerCu = 3;
+inline bool box_queue_candidate(const BoxGeom& g, int valid_mode, int cus, int box_kernel, int workgroups,
+                                int queue_workgroups) {
+    if (g.radius < 0 || g.radius > kMaxFastRadius || cus < 1) return false;
+    const int TW = box_tile_width(g.radius), dspan = g.d_hi - g.d_lo;
+    const int64_t tiles = (int64_t)((g.W + TW - 1) / TW) * ((g.H + kBoxTileH - 1) / kBoxTileH) * g.batch;
+    if (box_tile_kernel(g.radius, dspan, tiles, cus, box_kernel, box_mfma_scope(g, valid_mode)) != BoxTileKernel::Matrix)
+        return false;
+    return box_queue_workgroups(box_mfma_np(g.radius, dspan), dspan, box_mfma_tiles(g.W, g.H, g.radius, dspan, g.batch),
+                                kBoxMfmaWorkgroupsPerCu * cus, workgroups, queue_workgroups) > 0;
+}
+
 // Wide path: frames per vsum / hwta launch pair: enough row blocks for ~32 per CU (1080 rows of one 1080p frame
 // give 4), at most 8 frames and 4.5 GB of V planes (1080p D=128: 8 frames, 4.2 GB).  Same box, 1080p D=128, 8
 // frames per call (profiles/microbench/r05_wide_path.txt): 2 / 4 / 8 frames per pair 0.280 / 0.268 / 0.265 ms at

@@ -120,10 +120,15 @@ __device__ __forceinline__ uint32_t ld_image_u32(const uint8_t* p, int y, int x,
 // (bm_box_mfma.hip) wherever box_mfma_scope holds
 // box_workgroups (SM_PARAM_BOX_WORKGROUPS): workgroups of a matrix-pipe launch, each walking a contiguous range of
 // tiles: 0 auto, n >= 1 that many (at most one per tile)
-hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel = 0, int box_workgroups = 0);
+// box_queue: null, or the u32 counter from which an auto matrix-pipe launch draws its tiles where
+// box_queue_workgroups (bm_box_plan.h) says so; the launcher zeroes it on s.  box_queue_wgs
+// (SM_PARAM_BOX_QUEUE_WORKGROUPS): 0 one queue workgroup per resident slot, n >= 1 that many at any launch size
+hipError_t launch_box_match(const MatchArgs& a, int batch, hipStream_t s, int box_kernel = 0, int box_workgroups = 0,
+                            uint32_t* box_queue = nullptr, int box_queue_wgs = 0);
 // the plain box pass with both window sums on the matrix pipe: radius 1..kMaxFastRadius, valid_mode 0, no right
 // view; bit-exact with launch_box_match.  hipErrorInvalidValue outside box_mfma_scope (bm_box_plan.h)
-hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups = 0);
+hipError_t launch_box_match_mfma(const MatchArgs& a, int batch, hipStream_t s, int workgroups = 0,
+                                 uint32_t* queue = nullptr, int queue_workgroups = 0);
 // any radius: the direct window sum per (pixel, d), straight from the reference formulation; not a performance path
 hipError_t launch_box_match_generic(const MatchArgs& a, int batch, hipStream_t s);
 // Box matching + right view (+ LR check) in two launches (radius <= kMaxBoxRadius, d_lo == 0).

@@ -110,9 +110,17 @@ int run_box_pass(WsScope& ws, sm_handle* h, sm::MatchArgs a, int batch, const sm
     const bool fused = p.right == BoxRight::Fused;
     switch (p.left) {
         case BoxLeft::Tile:
-            if (!fused)
-                SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel, h->box_workgroups));
-            else if (r.keys)
+            if (!fused) {
+                // a matrix-pipe launch that may draw its tiles from the queue takes the handle's grab counter
+                uint32_t* queue = nullptr;
+                if (sm::box_queue_candidate(sm::box_geom(a, batch), a.valid_mode, sm::device_cus(), h->box_kernel,
+                                            h->box_workgroups, h->box_queue_workgroups)) {
+                    int rc = ws.get(h->boxq, sizeof(uint32_t), &queue);
+                    if (rc) return rc;
+                }
+                SM_HIP(sm::launch_box_match(a, batch, s, h->box_kernel, h->box_workgroups, queue,
+                                            h->box_queue_workgroups));
+            } else if (r.keys)
                 SM_HIP(sm::launch_box_slice_lr_keys(a, batch, r.keys, s));
             else
                 SM_HIP(sm::launch_box_match_lr(a, batch, r.check, r.map, r.mask, r.pitch, r.stride, s));
@@ -572,6 +580,7 @@ SM_API int sm_destroy(sm_handle* h) {
     (void)h->rpart.release();
     (void)h->vol.release();
     (void)h->spk.release();
+    (void)h->boxq.release();
     for (smh::DevBuf* b : {&h->aux, &h->maps, &h->bgr, &h->dsl}) (void)b->release();
     for (auto& ev : h->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -629,6 +638,13 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         if (!(value >= 0.f) || value > 16777216.f || (float)(int)value != value)
             return fail(SM_ERR_INVALID_ARG, "box workgroups must be an integer >= 0 (0 = auto)");
         h->box_workgroups = (int)value;
+        return SM_OK;
+    }
+    if (param == SM_PARAM_BOX_QUEUE_WORKGROUPS) {
+        if (!(value >= 0.f) || value > (float)sm::kMaxQueueWorkgroups || (float)(int)value != value)
+            return fail(SM_ERR_INVALID_ARG, "box queue workgroups must be an integer in [0, %d] (0 = auto)",
+                        sm::kMaxQueueWorkgroups);
+        h->box_queue_workgroups = (int)value;
         return SM_OK;
     }
     if (param == SM_PARAM_UNIQUENESS) {

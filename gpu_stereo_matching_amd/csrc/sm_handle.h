@@ -102,6 +102,7 @@ struct sm_handle {
     // whole 8-byte words at the planes' last bytes
     smh::SharedBuf vol{64};
     smh::SharedBuf spk;     // speckle filter: u32 labels and u32 counts of the frames in flight (bm_speckle_plan.h)
+    smh::SharedBuf boxq;    // matrix-pipe box launches that draw their tiles from a queue: the u32 grab counter
     // Staging of the host calls, grown on demand.  Only the handle's own stream touches them, in calls that end
     // in a synchronise, so they need no ordering:
     smh::DevBuf maps;   // float maps of the host remap / rectify-map calls
@@ -118,6 +119,7 @@ struct sm_handle {
     int stage_timing = 2;
     int box_kernel = 0;          // SM_PARAM_BOX_KERNEL: 0 auto, 1 VALU kernels, 2 matrix-pipe kernel
     int box_workgroups = 0;      // SM_PARAM_BOX_WORKGROUPS: 0 auto, n >= 1 workgroups per matrix-pipe launch
+    int box_queue_workgroups = 0;   // SM_PARAM_BOX_QUEUE_WORKGROUPS: 0 auto, n >= 1 queue workgroups at any launch size
     int uniqueness = 0;          // SM_PARAM_UNIQUENESS: 0 off, 1..99 the sub-pixel calls' uniqueness ratio
     int speckle_size = 0;        // SM_PARAM_SPECKLE_SIZE: 0 off, else the largest region the matching calls remove
     int speckle_range = 1;       // SM_PARAM_SPECKLE_RANGE: whole disparities joined into one region, 0..255

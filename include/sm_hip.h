@@ -139,8 +139,9 @@ enum {
     SM_PARAM_UNIQUENESS = 7,   /* uniqueness ratio of the sub-pixel calls (sm_match_subpix_device and friends): an
                                   integer 0..99, 0 (default) = off.  Other values: SM_ERR_INVALID_ARG */
     SM_PARAM_BOX_WORKGROUPS = 8, /* workgroups of a matrix-pipe box launch, each walking a contiguous range of tiles
-                                  and keeping the right band along a row of tiles: 0 (default) auto, 16 per
-                                  workgroup the device holds at once; an integer n >= 1 that many, at most one per
+                                  and keeping the right band along a row of tiles: 0 (default) auto (the queue of
+                                  SM_PARAM_BOX_QUEUE_WORKGROUPS, or 16 ranges per workgroup the device holds at
+                                  once); an integer n >= 1 that many, at most one per
                                   tile (n >= tiles: one tile per workgroup, nothing kept).  The maps and keys do not
                                   depend on it; the VALU kernels ignore it.  Other values: SM_ERR_INVALID_ARG */
     SM_PARAM_SPECKLE_SIZE = 9, /* StereoSGBM's speckleWindowSize: an integer >= 0 (at most 2^24), 0 (default) = off.
@@ -151,12 +152,18 @@ enum {
     SM_PARAM_SPECKLE_RANGE = 10, /* StereoSGBM's speckleRange: whole disparities, an integer 0..255, default 1.  The
                                   8-bit matching calls join neighbours with |a - b| <= range, the 1/16-px calls with
                                   |a - b| <= 16 * range, as StereoSGBM does on its 1/16-px map */
-    SM_PARAM_FILL_GAP = 11     /* the row fill's max_gap: an integer 0 .. 2^24, 0 (default) = off.  With a gap > 0
+    SM_PARAM_FILL_GAP = 11,    /* the row fill's max_gap: an integer 0 .. 2^24, 0 (default) = off.  With a gap > 0
                                   every matching call that returns a map ends with the row fill
                                   (sm_fill_invalid_device) on its final left map, after the median, the LR check and
                                   the speckle filter: runs of at most this many invalid pixels in a row take the
                                   smaller of their two neighbours.  Other values: SM_ERR_INVALID_ARG.  See "row fill"
                                   below for the calls that honour it and those that refuse it */
+    SM_PARAM_BOX_QUEUE_WORKGROUPS = 12 /* workgroups of a matrix-pipe box launch that draws its tiles from a queue
+                                  (SM_PARAM_BOX_WORKGROUPS 0, two disparities per pass): 0 (default) auto, one per
+                                  workgroup the device holds at once where each has enough tiles to draw, static
+                                  ranges elsewhere; an integer n in 1 .. 2^20 that many at any launch size, also more
+                                  than there are tiles.  The maps and keys do not depend on it.  Other values:
+                                  SM_ERR_INVALID_ARG */
 };
 
 typedef struct sm_handle sm_handle;

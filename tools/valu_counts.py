@@ -15,9 +15,10 @@ CTRS = "SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAV
 # symbol whose machine code tools/codeobj.py hashes into the entry: bench.py reports frac null when the library
 # it loads carries other code for that kernel)
 JOBS = (
-    # the headline launch runs the matrix-pipe kernel (bm_box_mfma.hip) in the default dispatch
-    ("box_r5_1080p_d128_b128", "box_mfma_kernel<5, 128, 2>", ["--agg", "box", "--batch", "128"],
-     [1920, 1080, 128, 5, 128], "box_mfma_kernelILi5ELi128ELi2EE"),
+    # the headline launch runs the matrix-pipe kernel (bm_box_mfma.hip) in the default dispatch, its workgroups
+    # drawing their tiles from the queue
+    ("box_r5_1080p_d128_b128", "box_mfma_queue_kernel<5, 128>", ["--agg", "box", "--batch", "128"],
+     [1920, 1080, 128, 5, 128], "box_mfma_queue_kernelILi5ELi128EE"),
     ("guided_r5_1080p_d128_b32", "guided_fused_kernel<5, false", ["--agg", "guided", "--batch", "32"],
      [1920, 1080, 128, 5, 32], "guided_fused_kernelILi5ELb0E"),
     ("guided_lr_r5_1080p_d128_b32", "guided_fused_kernel<5, true", ["--agg", "guided", "--lr", "--batch", "32"],
