@@ -194,6 +194,12 @@ class BlockMatcher:
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P1, float(int(p1))))
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_P2, float(int(p2))))
 
+    def set_sgm_paths(self, paths: int = 4):
+        """Scan directions agg='sgm' sums (SM_PARAM_SGM_PATHS): 4 (the default: along rows and columns) or 8, with
+        the four diagonals too, as libSGM's SCAN_8PATH and StereoSGBM's MODE_HH.  Four more path passes per frame;
+        the penalties, their bound and the workspace are the same.  Other values raise SMError."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_PATHS, float(paths)))
+
     def set_box_kernel(self, kernel: int = 0):
         """Which kernel the plain box pass runs (SM_PARAM_BOX_KERNEL): 0 auto by launch size, 1 the VALU kernels,
         2 the matrix-pipe kernel, at every launch size; same maps and keys.  2 outside its scope (lr_check,
@@ -905,6 +911,10 @@ class BlockMatcherGroup:
         """BlockMatcher.set_sgm_penalties on every member (agg='sgm' runs in match_batch only: whole frames)."""
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P1, float(int(p1))))
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_P2, float(int(p2))))
+
+    def set_sgm_paths(self, paths: int = 4):
+        """BlockMatcher.set_sgm_paths on every member (agg='sgm' runs in match_batch only: whole frames)."""
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_PATHS, float(paths)))
 
     def set_speckle(self, size: int = 0, range: int = 1):  # noqa: A002
         """BlockMatcher.set_speckle on every member: match_batch runs whole frames and honours it; the row-band

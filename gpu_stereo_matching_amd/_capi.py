@@ -39,6 +39,7 @@ SM_PARAM_SPECKLE_SIZE = 9
 SM_PARAM_SPECKLE_RANGE = 10
 SM_PARAM_FILL_GAP = 11
 SM_PARAM_BOX_QUEUE_WORKGROUPS = 12
+SM_PARAM_SGM_PATHS = 13
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (

@@ -146,6 +146,8 @@ def _main(argv=None) -> int:
     ap.add_argument("--agg", default="box", choices=["box", "guided", "sgm"])
     ap.add_argument("--cost", default="ad", choices=["ad", "census"],
                     help="matching cost: absolute difference, or census / Hamming (with --agg box or sgm, radius <= 7)")
+    ap.add_argument("--sgm-paths", type=int, default=4, choices=[4, 8],
+                    help="scan directions of --agg sgm: 4, or 8 with the diagonals (four more path passes)")
     ap.add_argument("--out", help="directory for disp_<n>.png")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -159,6 +161,7 @@ def _main(argv=None) -> int:
     first = next(iter(seq))
     H, W = first[1].shape[:2]
     with BlockMatcher(a.device, W, H, max(a.disp, 1)) as m:
+        m.set_sgm_paths(a.sgm_paths)
         maps = calib.rectify(m, *calib.load_data_batch(a.calib), (W, H)) if a.calib else None
         done = run_loop(seq, m, a.radius, a.disp, rectify_maps=maps, batch=a.batch, agg=a.agg, out_dir=a.out, cost=a.cost,
                         on_map=lambda n, d: print(f"pair {n}: {W}x{H}, {int((d > 0).sum())} matched pixels"))

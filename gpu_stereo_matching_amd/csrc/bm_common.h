@@ -195,11 +195,12 @@ hipError_t launch_box_match_strip_lr(const MatchArgs& a, int batch, uint32_t* ri
 size_t literal_workspace_bytes(int D);
 hipError_t launch_device_cu_literal(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int radius, int D,
                                     uint32_t* ws, uint8_t* out, int opitch, hipStream_t s);
-// semi-global matching (bm_sgm.hip): the four paths' sum S u32 [D][H][W], zeroed by the caller, from the u16 SAD
-// volume (0 <= P1 <= P2, 255 * win^2 + P2 <= 65535), and the WTA over it: the left map (smallest existing d at
+// semi-global matching (bm_sgm.hip): the paths' sum S u32 [D][H][W], zeroed by the caller, from the u16 SAD
+// volume (0 <= P1 <= P2, 255 * win^2 + P2 <= 65535; paths: 4, or 8 with the diagonals), and the WTA over it: the left map (smallest existing d at
 // min S, no threshold) and, when right_keys is given, the right view's keys [H][W], min over the d whose pair
 // (u + d, d) exists of (S(u + d, d) << 8 | d)
-hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, uint32_t* S, hipStream_t s);
+hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, uint32_t* S,
+                            hipStream_t s);
 hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
                           hipStream_t s);
 // the same WTA, thresholdless, over a u16 cost volume [D][H][W] (SM_COST_CENSUS with SM_AGG_BOX)

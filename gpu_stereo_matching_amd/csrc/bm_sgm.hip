@@ -1,13 +1,14 @@
-// bm_sgm.hip — semi-global matching (SM_AGG_SGM): four-path aggregation of the u16 box SAD volume and
-// the WTA over its sum.
+// bm_sgm.hip — semi-global matching (SM_AGG_SGM): four- or eight-path aggregation of the u16 box SAD volume and
+// the WTA over its sum (the diagonals §31).
 //
 // The recursion of one path direction rho, with q = p - rho the previous pixel on the path:
 //     L(p, d) = C(p, d)                                                              q outside the image
 //     L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + P1, L(q, d+1) + P1, M + P2) - M   M = min_k L(q, k)
 // over the pairs (x, d) that exist (x + d <= W, Device.cu:44).  A pair that does not exist is carried as
 // kInf, which loses every min, so the "dropped terms" of the definition need no branches.  L <= C + P2 fits
-// u16 (the entry points check 255 * win^2 + P2 <= 65535); the sum S of the four directions is u32 [D][H][W],
-// zeroed by the caller and accumulated with no-return global atomic adds, so the four directions need no
+// u16 (the entry points check 255 * win^2 + P2 <= 65535); the sum S of the four directions (+-1, 0), (0, +-1), and
+// with SM_PARAM_SGM_PATHS 8 of the four diagonals (+-1, +-1) too, is u32 [D][H][W] (< 2^18, with eight < 2^19),
+// zeroed by the caller and accumulated with no-return global atomic adds, so the directions need no
 // order among themselves and integer addition keeps the sum exact.
 #include "bm_common.h"
 
@@ -190,11 +191,98 @@ __global__ __launch_bounds__(1024) void sgm_v_kernel(const uint16_t* __restrict_
     }
 }
 
+// ---- diagonal paths (SM_PARAM_SGM_PATHS 8): sgm_v_kernel's workgroup with columns that slide along the path ----
+// rho = (dx, dy) with dx, dy = +-1.  At step s of the walk (row y0 + s * dy) lane l of tile t is at the column
+//     x = (32 t + l + s * dx) mod Wp,   Wp = 32 * ceil(W / 32),
+// so the columns of all tiles cover every row exactly once, a lane's previous pixel on the path, q = p - rho, is the
+// one it held a row earlier, and its L stays in its registers.  A lane restarts its path (L = C) in the first row of
+// the walk and where x - dx is outside [0, W): the column the path enters by, which is also where the wrap brings a
+// lane back into the frame.  A lane at a column >= W (the padding of the last tile) is idle: it loads and adds
+// nothing and carries kInf.  The 32 columns of a half wave stay one row segment, cut in two only at the wrap, so the
+// cost loads and the atomic adds keep the vertical kernel's shape, shifted by s columns.  The d that exist change
+// with the column: dmax is per lane and row here, and the prefetch queue follows the column kPF rows ahead.
+template <int DPT>
+__global__ __launch_bounds__(1024) void sgm_d_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
+                                                     uint32_t P2, uint32_t* __restrict__ S) {
+    __shared__ uint32_t ex[2][3][32][kVX];
+    const int lane = threadIdx.x & (kVX - 1), w = threadIdx.x / kVX, nw = blockDim.x / kVX;
+    const int Wp = (int)gridDim.x * kVX;
+    const int dir = blockIdx.y;   // rho = (+1, +1), (-1, +1), (+1, -1), (-1, -1)
+    const int dx = dir & 1 ? -1 : 1, dy = dir & 2 ? -1 : 1;
+    const int64_t P = (int64_t)W * H;
+    const int d0 = w * DPT;
+    const int y0 = dy < 0 ? H - 1 : 0;
+    // one step along the row, modulo Wp
+    auto slide = [&](int x) {
+        x += dx;
+        return x < 0 ? x + Wp : (x >= Wp ? x - Wp : x);
+    };
+    auto dmax_at = [&](int x) { return x < W ? min(D - 1, W - x) : -1; };   // d <= dmax exist at this column
+    uint32_t Lp[DPT], Cq[kPF][DPT];
+#pragma unroll
+    for (int j = 0; j < DPT; ++j) Lp[j] = kInf;
+    int x = blockIdx.x * kVX + lane;   // this row's column
+    int xq = x;                        // the column of the next row to enter the queue
+#pragma unroll
+    for (int u = 0; u < kPF; ++u) {
+        const int dm = dmax_at(xq);
+#pragma unroll
+        for (int j = 0; j < DPT; ++j)
+            Cq[u][j] = u < H && d0 + j <= dm ? C[(d0 + j) * P + (int64_t)(y0 + u * dy) * W + xq] : 0u;
+        xq = slide(xq);
+    }
+    for (int s0 = 0; s0 < H; s0 += kPF) {
+#pragma unroll
+        for (int u = 0; u < kPF; ++u) {
+            const int s = s0 + u;
+            if (s >= H) break;   // uniform over the workgroup
+            const int y = y0 + s * dy;
+            const int dmax = dmax_at(x);
+            const int xp = x - dx;                                // q's column, before the wrap
+            const bool restart = s == 0 || xp < 0 || xp >= W;
+            const int dmq = dmax_at(xq);
+            uint32_t Cc[DPT];
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) {   // this row's costs out of the queue, row s + kPF's into it
+                Cc[j] = Cq[u][j];
+                if (s + kPF < H) Cq[u][j] = d0 + j <= dmq ? C[(d0 + j) * P + (int64_t)(y + kPF * dy) * W + xq] : 0u;
+            }
+            uint32_t m = Lp[0];
+#pragma unroll
+            for (int j = 1; j < DPT; ++j) m = min(m, Lp[j]);
+            const int b = u & 1;   // kPF is even: the parity of s
+            ex[b][0][w][lane] = m;
+            ex[b][1][w][lane] = Lp[0];
+            ex[b][2][w][lane] = Lp[DPT - 1];
+            __syncthreads();
+            uint32_t M = kInf;
+            for (int k = 0; k < nw; ++k) M = min(M, ex[b][0][k][lane]);
+            const uint32_t lo = w > 0 ? ex[b][2][w - 1][lane] : kInf;
+            const uint32_t hi = w + 1 < nw ? ex[b][1][w + 1][lane] : kInf;
+            uint32_t Ln[DPT];
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) {
+                const uint32_t below = j > 0 ? Lp[j > 0 ? j - 1 : 0] : lo;
+                const uint32_t above = j < DPT - 1 ? Lp[j < DPT - 1 ? j + 1 : 0] : hi;
+                const uint32_t best = min(min(Lp[j], below + P1), min(above + P1, M + P2));
+                const uint32_t v = restart ? Cc[j] : Cc[j] + best - M;
+                const bool exists = d0 + j <= dmax;
+                if (exists) atomicAdd(&S[(d0 + j) * P + (int64_t)y * W + x], v);
+                Ln[j] = exists ? v : kInf;
+            }
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) Lp[j] = Ln[j];
+            x = slide(x);
+            xq = slide(xq);
+        }
+    }
+}
+
 // ---- WTA over S: the left map and, when asked, the right view's keys ----
 // Left: the smallest existing d (d <= W - x) attaining min S, no threshold.  Right view: S_R(y, u, d) =
 // S(y, u + d, d) (StereoHelper.cpp:156-180) over the d whose pair (u + d, d) exists, u + 2 d <= W (which
 // implies u + d < W; d = 0 always exists); key = S << 8 | d, whose low byte is dR.
-// T: uint32_t, the paths' sum S (< 2^18), or uint16_t, a box cost volume taken without SGM (SM_COST_CENSUS with
+// T: uint32_t, the paths' sum S (< 2^19 with eight paths), or uint16_t, a box cost volume taken without SGM (SM_COST_CENSUS with
 // SM_AGG_BOX: the census cost, <= 62 * win^2 = 13950); either key fits 32 bits.
 template <typename T>
 __global__ __launch_bounds__(256) void sgm_wta_kernel(const T* __restrict__ S, int W, int H, int D,
@@ -219,8 +307,10 @@ __global__ __launch_bounds__(256) void sgm_wta_kernel(const T* __restrict__ S, i
 
 }  // namespace
 
-hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, uint32_t* S, hipStream_t s) {
+hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, uint32_t* S,
+                            hipStream_t s) {
     if (W <= 0 || H <= 0 || D < 1 || D > kMaxDisp || P1 < 0 || P2 < P1 || P2 > 65535) return hipErrorInvalidValue;
+    if (paths != 4 && paths != 8) return hipErrorInvalidValue;
     const dim3 hgrid((unsigned)H, 2);
     const int nj = (D + 63) / 64;
 #define SM_SGM_H(n)                                                                                                  \
@@ -248,6 +338,14 @@ hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, in
     else if (dpt == 4) SM_SGM_V(4);
     else SM_SGM_V(8);
 #undef SM_SGM_V
+    e = hipGetLastError();
+    if (e != hipSuccess || paths == 4) return e;
+    const dim3 dgrid(vgrid.x, 4);   // the four diagonals: the vertical pass's tiles and chunks
+#define SM_SGM_D(n) hipLaunchKernelGGL(sgm_d_kernel<n>, dgrid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, S)
+    if (dpt == 2) SM_SGM_D(2);
+    else if (dpt == 4) SM_SGM_D(4);
+    else SM_SGM_D(8);
+#undef SM_SGM_D
     return hipGetLastError();
 }
 

@@ -627,6 +627,12 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         (param == SM_PARAM_SGM_P1 ? h->sgm_p1 : h->sgm_p2) = v;
         return SM_OK;
     }
+    if (param == SM_PARAM_SGM_PATHS) {
+        if (value != 4.f && value != 8.f)
+            return fail(SM_ERR_INVALID_ARG, "SGM paths must be 4 or 8 (8 adds the four diagonal paths)");
+        h->sgm_paths = (int)value;
+        return SM_OK;
+    }
     if (param == SM_PARAM_BOX_KERNEL) {
         if (value != 0.f && value != 1.f && value != 2.f)
             return fail(SM_ERR_INVALID_ARG, "box kernel is 0 (auto), 1 (legacy) or 2 (matrix)");

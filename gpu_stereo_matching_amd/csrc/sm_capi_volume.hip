@@ -52,7 +52,7 @@ int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out
 // Every pass that keeps a cost volume, over `batch` frames, one frame after another through the volume workspace
 // (volume_layout):
 //   cost volume (AD, or the census words of both frames and their Hamming volume) -> box sums (u16)
-//   -> with SGM the zeroed S and the four paths' sums over it
+//   -> with SGM the zeroed S and the paths' sums over it (the handle's sgm_paths: four, or eight with the diagonals)
 //   -> one winner-takes-all over S (SGM) or the u16 costs: 8-bit maps with the right view's keys and their low
 //      byte, or subpix_wta_kernel (-> LR check; the two views' d0 of the check take the right-keys region).
 int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
@@ -90,7 +90,7 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
         SM_HIP(sm::launch_box_sad_volume(vol, W, H, radius, D, cost, s));
         if (sgm) {
             SM_HIP(hipMemsetAsync(S, 0, (size_t)(4 * P * D), s));
-            SM_HIP(sm::launch_sgm_paths(cost, W, H, D, p1, p2, S, s));
+            SM_HIP(sm::launch_sgm_paths(cost, W, H, D, p1, p2, h->sgm_paths, S, s));
         }
         if (subpix) {
             uint16_t* out = o.disp16 + f * o.ostride;

@@ -114,6 +114,7 @@ struct sm_handle {
     float guided_eps = 6.5025f;  // 1e-4 * 255^2 (AD units)
     int staged_group = 8;        // SM_STAGED frames per launch group (SM_PARAM_STAGED_GROUP)
     int sgm_p1 = 0, sgm_p2 = 0;  // SM_AGG_SGM penalties (SM_PARAM_SGM_P1 / _P2), 0 = auto
+    int sgm_paths = 4;           // SM_PARAM_SGM_PATHS: 4 scan directions, or 8 with the diagonals
     // host calls record the upload / match / download split (SM_PARAM_STAGE_TIMING): 0 off, 1 on, 2 auto
     // (default: on once sm_last_stage_ms has been called on the handle, or when SM_VERBOSE is set)
     int stage_timing = 2;

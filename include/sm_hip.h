@@ -71,10 +71,11 @@ enum {
     SM_AGG_SGM = 32u,       /* semi-global matching (this build's extension) on the box SAD cost C(d, y, x) (the
                                zero-padded (2r+1)^2 SAD of sm_sad_volume_device), radius <= 7, width <= 4096.  Over
                                the pairs that exist, x + d <= W (Device.cu:44), and the four directions rho =
-                               (+-1, 0), (0, +-1), with q = p - rho:
+                               (+-1, 0), (0, +-1) by default, the eight with the diagonals (+-1, +-1) too when
+                               SM_PARAM_SGM_PATHS is 8, with q = p - rho:
                                  L(p, d) = C(p, d)                                          q outside the image
                                  L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + P1, L(q, d+1) + P1, M + P2) - M,
-                                 M = min_k L(q, k);   S = sum of the four L.
+                                 M = min_k L(q, k);   S = sum of the four (or eight) L.
                                Left map: the smallest existing d at min S, no 50*win^2 threshold (S is no SAD).
                                Right view (SM_LR_CHECK): S_R(u, d) = S(u + d, d) over the d whose pair (u + d, d)
                                exists (u + 2d <= W), first minimum; then the usual check.  SM_MEDIAN filters both
@@ -158,12 +159,19 @@ enum {
                                   the speckle filter: runs of at most this many invalid pixels in a row take the
                                   smaller of their two neighbours.  Other values: SM_ERR_INVALID_ARG.  See "row fill"
                                   below for the calls that honour it and those that refuse it */
-    SM_PARAM_BOX_QUEUE_WORKGROUPS = 12 /* workgroups of a matrix-pipe box launch that draws its tiles from a queue
+    SM_PARAM_BOX_QUEUE_WORKGROUPS = 12, /* workgroups of a matrix-pipe box launch that draws its tiles from a queue
                                   (SM_PARAM_BOX_WORKGROUPS 0, two disparities per pass): 0 (default) auto, one per
                                   workgroup the device holds at once where each has enough tiles to draw, static
                                   ranges elsewhere; an integer n in 1 .. 2^20 that many at any launch size, also more
                                   than there are tiles.  The maps and keys do not depend on it.  Other values:
                                   SM_ERR_INVALID_ARG */
+    SM_PARAM_SGM_PATHS = 13    /* scan directions SM_AGG_SGM sums: 4 (default), rho = (+-1, 0), (0, +-1), or 8, those
+                                  and the diagonals (+1, +1), (-1, +1), (+1, -1), (-1, -1), each under the same
+                                  recursion, existence rule and penalties (a diagonal path starts, L = C, in the first
+                                  row of its walk and in the column it enters the frame by).  S <= 8 * 65535 < 2^19;
+                                  sm_sgm_check and sm_sgm_workspace_bytes do not depend on it, and everything after S
+                                  (both views' WTA, median, LR check, the sub-pixel calls, speckle, fill) is
+                                  unchanged.  Four more path passes per frame.  Other values: SM_ERR_INVALID_ARG */
 };
 
 typedef struct sm_handle sm_handle;

@@ -4,6 +4,9 @@ Writes profiles/sgm_bench.json: ms per frame, the algorithmic bytes of the desig
 and that traffic over the time as a fraction of the 6.85 TB/s fill rate the project measured
 (profiles/microbench/r05_write_ceiling.txt).  No GPU, no number: the script fails without one.
 
+--paths 8 times the same two calls with the diagonal paths on (SM_PARAM_SGM_PATHS 8) and writes
+profiles/sgm_bench_paths8.json; the default, 4, writes the files named here.
+
 --cost census times the census cost (SM_COST_CENSUS) under --agg sgm or box instead, beside AD SGM from the same run
 of the same build, and writes profiles/census_bench.json (ms per map only: DESIGN §18).
 
@@ -32,8 +35,13 @@ FORMULA = {
 }
 
 
-def algorithmic_bytes(P, D, lr):
+FORMULA_DIAGONAL = "4 * (2*P*D + 8*P*D)  (--paths 8: the same per direction, four diagonals)"
+
+
+def algorithmic_bytes(P, D, lr, paths=4):
     b = (2 * P + P * D) + 3 * P * D + 4 * P * D + 2 * 10 * P * D + 2 * 10 * P * D + (4 * P * D + P)
+    if paths == 8:
+        b += 4 * 10 * P * D
     if lr:
         b += 4 * P * D + 4 * P + 4 * P + P + 3 * P
     return b
@@ -133,6 +141,9 @@ def main(argv=None):
     ap.add_argument("--cost", default="ad", choices=["ad", "census"])
     ap.add_argument("--agg", default="sgm", choices=["sgm", "box"])
     ap.add_argument("--subpix", action="store_true", help="time the sub-pixel call against the 8-bit call (AD and census SGM)")
+    ap.add_argument("--paths", type=int, default=4, choices=[4, 8],
+                    help="scan directions of AD SGM (SM_PARAM_SGM_PATHS): 8 adds the diagonals and writes "
+                         "profiles/sgm_bench_paths8.json")
     ap.add_argument("--out", default=None,
                     help="default: profiles/sgm_bench.json, census_bench.json with --cost census, subpix_bench.json with --subpix")
     a = ap.parse_args(argv)
@@ -140,8 +151,12 @@ def main(argv=None):
         ap.error("--iters must be at least 20")
     if a.cost == "ad" and a.agg != "sgm":
         ap.error("--agg box is timed with --cost census only (the AD box path is bench.py's)")
+    if a.paths == 8 and (a.subpix or a.cost != "ad"):
+        ap.error("--paths 8 is timed on the AD SGM calls only")
     if a.out is None:
         name = "subpix_bench.json" if a.subpix else ("sgm_bench.json" if a.cost == "ad" else "census_bench.json")
+        if a.paths == 8:
+            name = "sgm_bench_paths8.json"
         a.out = os.path.join(ROOT, "profiles", name)
     import torch
     import gpu_stereo_matching_amd as sm
@@ -160,7 +175,12 @@ def main(argv=None):
            "device": torch.cuda.get_device_name(0), "warmup": a.warmup, "iters": a.iters,
            "workspace_bytes": sm.sgm_workspace_bytes(W, H, D, r),
            "algorithmic_bytes_formula": FORMULA, "fill_rate_bytes_per_s": FILL_BYTES_PER_S, "runs": {}}
+    if a.paths == 8:
+        res["workload"]["paths"] = 8
+        res["algorithmic_bytes_formula"] = dict(FORMULA, paths_diagonal=FORMULA_DIAGONAL)
     with sm.BlockMatcher(0, W, H, D) as m:
+        if a.paths != 4:
+            m.set_sgm_paths(a.paths)
         for name, lr in (("sgm", False), ("sgm_lr", True)):
             for _ in range(a.warmup):
                 m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr)
@@ -172,7 +192,7 @@ def main(argv=None):
             e1.record()
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / a.iters
-            nbytes = algorithmic_bytes(P, D, lr)
+            nbytes = algorithmic_bytes(P, D, lr, a.paths)
             res["runs"][name] = {"ms_per_frame": round(ms, 4), "algorithmic_bytes": nbytes,
                                  "algorithmic_GB_per_s": round(nbytes / ms / 1e6, 1),
                                  "fraction_of_fill_rate": round(nbytes / (ms * 1e-3) / FILL_BYTES_PER_S, 4),
