@@ -47,6 +47,17 @@ __device__ __forceinline__ uint32_t from_lane_above(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)kInf, (int)v, kDppWaveShl1, 0xF, 0xF, false);
 }
 
+// The recursion's min for register j of a lane's N consecutive d: Lp is L(q, .) of those d, lo and hi are L(q, .) of
+// the d below the lane's first and above its last.  The caller finishes the update, L = restart ? C : C + best - M;
+// with that select in here the column kernel compiles to more registers.
+template <int N>
+__device__ __forceinline__ uint32_t path_best(const uint32_t (&Lp)[N], int j, uint32_t lo, uint32_t hi, uint32_t M,
+                                              uint32_t P1, uint32_t P2) {
+    const uint32_t below = j > 0 ? Lp[j > 0 ? j - 1 : 0] : lo;
+    const uint32_t above = j < N - 1 ? Lp[j < N - 1 ? j + 1 : 0] : hi;
+    return min(min(Lp[j], below + P1), min(above + P1, M + P2));
+}
+
 // ---- horizontal paths: one wave per (row, direction), disparities across the lanes ----
 // Lane l holds d = l * NJ .. l * NJ + NJ - 1 (NJ = ceil(D / 64)): d +- 1 is a register of the same lane
 // except at the lane's two ends, which take one wave shift each; M is the lanes' min (wave_min).  The volume
@@ -102,9 +113,7 @@ __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ 
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const uint32_t c = tile[lane * LS + j * kTX + xi];
-                const uint32_t below = j > 0 ? Lp[j > 0 ? j - 1 : 0] : lo;
-                const uint32_t above = j < NJ - 1 ? Lp[j < NJ - 1 ? j + 1 : 0] : hi;
-                const uint32_t best = min(min(Lp[j], below + P1), min(above + P1, M + P2));
+                const uint32_t best = path_best(Lp, j, lo, hi, M, P1, P2);
                 const uint32_t v = first ? c : c + best - M;
                 tile[lane * LS + j * kTX + xi] = (uint16_t)v;
                 Ln[j] = lane * NJ + j <= dmax ? v : kInf;
@@ -124,112 +133,51 @@ __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ 
     }
 }
 
-// ---- vertical paths: one workgroup per (32-column tile, direction), columns across the lanes ----
+// ---- vertical and diagonal paths: one workgroup per (32-column tile, direction), columns across the lanes ----
 // Half wave w holds d = w * DPT .. w * DPT + DPT - 1 of its 32 columns in registers and walks the rows; every
 // cost and sum access is a coalesced row segment (64 B of costs, 128 B of sums).  Per row the waves exchange, through a double-buffered
 // LDS block and one barrier, their partial min (for M) and their first and last L (the d +- 1 terms at the
 // chunk ends).  The costs of the next kPF rows are always in flight: a row's loads are issued kPF rows ahead.
-constexpr int kPF = 4;
-constexpr int kVX = 32;   // columns per vertical workgroup: each half of a wave is one d chunk of 32 columns
-template <int DPT>
-__global__ __launch_bounds__(1024) void sgm_v_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
-                                                     uint32_t P2, uint32_t* __restrict__ S) {
-    __shared__ uint32_t ex[2][3][32][kVX];
-    const int lane = threadIdx.x & (kVX - 1), w = threadIdx.x / kVX, nw = blockDim.x / kVX;
-    const int x = blockIdx.x * kVX + lane;
-    const int dir = blockIdx.y;   // 0: rho = (0, +1), top to bottom; 1: rho = (0, -1)
-    const int64_t P = (int64_t)W * H;
-    const int d0 = w * DPT;
-    const int dmax = x < W ? min(D - 1, W - x) : -1;   // d <= dmax exist in this column (every row alike)
-    uint32_t Lp[DPT], Cq[kPF][DPT];
-    const int y0 = dir ? H - 1 : 0, dy = dir ? -1 : 1;
-#pragma unroll
-    for (int j = 0; j < DPT; ++j) Lp[j] = kInf;
-#pragma unroll
-    for (int u = 0; u < kPF; ++u)
-#pragma unroll
-        for (int j = 0; j < DPT; ++j)
-            Cq[u][j] = u < H && d0 + j <= dmax ? C[(d0 + j) * P + (int64_t)(y0 + u * dy) * W + x] : 0u;
-    for (int s0 = 0; s0 < H; s0 += kPF) {
-#pragma unroll
-        for (int u = 0; u < kPF; ++u) {
-            const int s = s0 + u;
-            if (s >= H) break;   // uniform over the workgroup
-            const int y = y0 + s * dy;
-            uint32_t Cc[DPT];
-#pragma unroll
-            for (int j = 0; j < DPT; ++j) {   // this row's costs out of the queue, row s + kPF's into it
-                Cc[j] = Cq[u][j];
-                if (s + kPF < H) Cq[u][j] = d0 + j <= dmax ? C[(d0 + j) * P + (int64_t)(y + kPF * dy) * W + x] : 0u;
-            }
-            uint32_t m = Lp[0];
-#pragma unroll
-            for (int j = 1; j < DPT; ++j) m = min(m, Lp[j]);
-            const int b = u & 1;   // kPF is even: the parity of s
-            ex[b][0][w][lane] = m;
-            ex[b][1][w][lane] = Lp[0];
-            ex[b][2][w][lane] = Lp[DPT - 1];
-            __syncthreads();
-            uint32_t M = kInf;
-            for (int k = 0; k < nw; ++k) M = min(M, ex[b][0][k][lane]);
-            const uint32_t lo = w > 0 ? ex[b][2][w - 1][lane] : kInf;
-            const uint32_t hi = w + 1 < nw ? ex[b][1][w + 1][lane] : kInf;
-            uint32_t Ln[DPT];
-#pragma unroll
-            for (int j = 0; j < DPT; ++j) {
-                const uint32_t below = j > 0 ? Lp[j > 0 ? j - 1 : 0] : lo;
-                const uint32_t above = j < DPT - 1 ? Lp[j < DPT - 1 ? j + 1 : 0] : hi;
-                const uint32_t best = min(min(Lp[j], below + P1), min(above + P1, M + P2));
-                const uint32_t v = s == 0 ? Cc[j] : Cc[j] + best - M;
-                const bool exists = d0 + j <= dmax;
-                if (exists) atomicAdd(&S[(d0 + j) * P + (int64_t)y * W + x], v);
-                Ln[j] = exists ? v : kInf;
-            }
-#pragma unroll
-            for (int j = 0; j < DPT; ++j) Lp[j] = Ln[j];
-        }
-    }
-}
-
-// ---- diagonal paths (SM_PARAM_SGM_PATHS 8): sgm_v_kernel's workgroup with columns that slide along the path ----
-// rho = (dx, dy) with dx, dy = +-1.  At step s of the walk (row y0 + s * dy) lane l of tile t is at the column
+// !DIAG, rho = (0, +-1): a lane keeps its column, restarts its path (L = C) in the first row only, and the d that
+// exist, d <= dmax, are the same in every row.  What follows is switched on by DIAG at compile time, not by dx.
+// DIAG (SM_PARAM_SGM_PATHS 8), rho = (dx, dy) with dx, dy = +-1: the columns slide along the path.  At step s of the
+// walk (row y0 + s * dy) lane l of tile t is at the column
 //     x = (32 t + l + s * dx) mod Wp,   Wp = 32 * ceil(W / 32),
 // so the columns of all tiles cover every row exactly once, a lane's previous pixel on the path, q = p - rho, is the
-// one it held a row earlier, and its L stays in its registers.  A lane restarts its path (L = C) in the first row of
-// the walk and where x - dx is outside [0, W): the column the path enters by, which is also where the wrap brings a
-// lane back into the frame.  A lane at a column >= W (the padding of the last tile) is idle: it loads and adds
-// nothing and carries kInf.  The 32 columns of a half wave stay one row segment, cut in two only at the wrap, so the
-// cost loads and the atomic adds keep the vertical kernel's shape, shifted by s columns.  The d that exist change
-// with the column: dmax is per lane and row here, and the prefetch queue follows the column kPF rows ahead.
-template <int DPT>
-__global__ __launch_bounds__(1024) void sgm_d_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
-                                                     uint32_t P2, uint32_t* __restrict__ S) {
+// one it held a row earlier, and its L stays in its registers.  A lane restarts also where x - dx is outside [0, W):
+// the column the path enters by, which is also where the wrap brings a lane back into the frame.  A lane at a
+// column >= W (the padding of the last tile) is idle: it loads and adds nothing and carries kInf.  The 32 columns of
+// a half wave stay one row segment, cut in two only at the wrap, so the cost loads and the atomic adds keep their
+// shape, shifted by s columns.  The d that exist change with the column: dmax is per lane and row, and the prefetch
+// queue follows the column kPF rows ahead.
+constexpr int kPF = 4;
+constexpr int kVX = 32;   // columns per workgroup: each half of a wave is one d chunk of 32 columns
+template <int DPT, bool DIAG>
+__global__ __launch_bounds__(1024) void sgm_col_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
+                                                       uint32_t P2, uint32_t* __restrict__ S) {
     __shared__ uint32_t ex[2][3][32][kVX];
     const int lane = threadIdx.x & (kVX - 1), w = threadIdx.x / kVX, nw = blockDim.x / kVX;
     const int Wp = (int)gridDim.x * kVX;
-    const int dir = blockIdx.y;   // rho = (+1, +1), (-1, +1), (+1, -1), (-1, -1)
-    const int dx = dir & 1 ? -1 : 1, dy = dir & 2 ? -1 : 1;
+    const int dir = blockIdx.y;   // rho = (0, +1), (0, -1); DIAG: (+1, +1), (-1, +1), (+1, -1), (-1, -1)
+    const int dx = !DIAG ? 0 : (dir & 1 ? -1 : 1), dy = (DIAG ? dir & 2 : dir) ? -1 : 1;
     const int64_t P = (int64_t)W * H;
     const int d0 = w * DPT;
     const int y0 = dy < 0 ? H - 1 : 0;
-    // one step along the row, modulo Wp
-    auto slide = [&](int x) {
-        x += dx;
-        return x < 0 ? x + Wp : (x >= Wp ? x - Wp : x);
-    };
+    // DIAG: one step along the row, modulo Wp
+    auto slide = [&](int x) { x += dx; return x < 0 ? x + Wp : (x >= Wp ? x - Wp : x); };
     auto dmax_at = [&](int x) { return x < W ? min(D - 1, W - x) : -1; };   // d <= dmax exist at this column
     uint32_t Lp[DPT], Cq[kPF][DPT];
 #pragma unroll
     for (int j = 0; j < DPT; ++j) Lp[j] = kInf;
-    int x = blockIdx.x * kVX + lane;   // this row's column
-    int xq = x;                        // the column of the next row to enter the queue
+    int x = blockIdx.x * kVX + lane, dmax = dmax_at(x);   // this row's column and its dmax; they change with DIAG only
+    int xq = x, dmq = dmax;                               // those of the next row to enter the queue
 #pragma unroll
     for (int u = 0; u < kPF; ++u) {
-        const int dm = dmax_at(xq);
+        if (DIAG) dmq = dmax_at(xq);
 #pragma unroll
         for (int j = 0; j < DPT; ++j)
-            Cq[u][j] = u < H && d0 + j <= dm ? C[(d0 + j) * P + (int64_t)(y0 + u * dy) * W + xq] : 0u;
-        xq = slide(xq);
+            Cq[u][j] = u < H && d0 + j <= dmq ? C[(d0 + j) * P + (int64_t)(y0 + u * dy) * W + xq] : 0u;
+        if (DIAG) xq = slide(xq);
     }
     for (int s0 = 0; s0 < H; s0 += kPF) {
 #pragma unroll
@@ -237,10 +185,9 @@ __global__ __launch_bounds__(1024) void sgm_d_kernel(const uint16_t* __restrict_
             const int s = s0 + u;
             if (s >= H) break;   // uniform over the workgroup
             const int y = y0 + s * dy;
-            const int dmax = dmax_at(x);
-            const int xp = x - dx;                                // q's column, before the wrap
-            const bool restart = s == 0 || xp < 0 || xp >= W;
-            const int dmq = dmax_at(xq);
+            if (DIAG) dmax = dmax_at(x), dmq = dmax_at(xq);
+            const int xp = x - dx;                                          // q's column, before the wrap
+            const bool restart = s == 0 || (DIAG && (xp < 0 || xp >= W));
             uint32_t Cc[DPT];
 #pragma unroll
             for (int j = 0; j < DPT; ++j) {   // this row's costs out of the queue, row s + kPF's into it
@@ -262,9 +209,7 @@ __global__ __launch_bounds__(1024) void sgm_d_kernel(const uint16_t* __restrict_
             uint32_t Ln[DPT];
 #pragma unroll
             for (int j = 0; j < DPT; ++j) {
-                const uint32_t below = j > 0 ? Lp[j > 0 ? j - 1 : 0] : lo;
-                const uint32_t above = j < DPT - 1 ? Lp[j < DPT - 1 ? j + 1 : 0] : hi;
-                const uint32_t best = min(min(Lp[j], below + P1), min(above + P1, M + P2));
+                const uint32_t best = path_best(Lp, j, lo, hi, M, P1, P2);
                 const uint32_t v = restart ? Cc[j] : Cc[j] + best - M;
                 const bool exists = d0 + j <= dmax;
                 if (exists) atomicAdd(&S[(d0 + j) * P + (int64_t)y * W + x], v);
@@ -272,8 +217,7 @@ __global__ __launch_bounds__(1024) void sgm_d_kernel(const uint16_t* __restrict_
             }
 #pragma unroll
             for (int j = 0; j < DPT; ++j) Lp[j] = Ln[j];
-            x = slide(x);
-            xq = slide(xq);
+            if (DIAG) x = slide(x), xq = slide(xq);
         }
     }
 }
@@ -333,19 +277,14 @@ hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, in
     const int dpt = D <= 64 ? 2 : (D <= 128 ? 4 : 8);   // at most 32 chunks of d
     // whole waves: a last half wave beyond D holds no existing d and only takes part in the exchange
     const dim3 vblock((unsigned)((kVX * ((D + dpt - 1) / dpt) + 63) / 64 * 64));
-#define SM_SGM_V(n) hipLaunchKernelGGL(sgm_v_kernel<n>, vgrid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, S)
-    if (dpt == 2) SM_SGM_V(2);
-    else if (dpt == 4) SM_SGM_V(4);
-    else SM_SGM_V(8);
-#undef SM_SGM_V
+#define SM_SGM_COL(diag, grid)                                                                                       \
+    hipLaunchKernelGGL((dpt == 2 ? sgm_col_kernel<2, diag> : (dpt == 4 ? sgm_col_kernel<4, diag> : sgm_col_kernel<8, diag>)), \
+                       grid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, S)
+    SM_SGM_COL(false, vgrid);
     e = hipGetLastError();
     if (e != hipSuccess || paths == 4) return e;
-    const dim3 dgrid(vgrid.x, 4);   // the four diagonals: the vertical pass's tiles and chunks
-#define SM_SGM_D(n) hipLaunchKernelGGL(sgm_d_kernel<n>, dgrid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, S)
-    if (dpt == 2) SM_SGM_D(2);
-    else if (dpt == 4) SM_SGM_D(4);
-    else SM_SGM_D(8);
-#undef SM_SGM_D
+    SM_SGM_COL(true, dim3(vgrid.x, 4));   // the four diagonals: the vertical pass's tiles and chunks
+#undef SM_SGM_COL
     return hipGetLastError();
 }
 

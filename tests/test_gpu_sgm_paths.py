@@ -1,7 +1,8 @@
 """GPU SGM with eight paths (SM_PARAM_SGM_PATHS 8) against the numpy restatement (tests/sgm_paths_ref.py).
 
 Every shape runs through match, match_lr, match_subpix and match_subpix with the LR check and uniqueness 10, on the
-AD and the census cost.  The sub-pixel maps matter: they depend on S itself, where the 8-bit maps can agree between
+AD and the census cost; the shapes of test_shapes run with four paths as well, through the same kernel's vertical
+form.  The sub-pixel maps matter: they depend on S itself, where the 8-bit maps can agree between
 four and eight paths.  Integer arithmetic end to end: every comparison is np.array_equal.
 """
 import functools
@@ -85,13 +86,13 @@ def wide_matcher(sm_mod):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(case):
-    """(L, R, reference) of a shape, computed once and shared by its costs."""
+def _case(case, paths=8):
+    """(L, R, reference) of a shape and a path count, computed once and shared by its costs."""
     W, H, D, r = case
     L, R = fuzz_pair(np.random.default_rng(W * 131 + H * 17 + D), W, H)
     L.setflags(write=False)
     R.setflags(write=False)
-    return L, R, PathsReference(_oracle(), L, R, r, D)
+    return L, R, PathsReference(_oracle(), L, R, r, D, paths=paths)
 
 
 def _check(m, L, R, r, D, cost, ref, combos, tag):
@@ -116,15 +117,23 @@ def _check(m, L, R, r, D, cost, ref, combos, tag):
 
 
 # ---- 1. the shapes ----
+# With four paths too: the vertical walk is the diagonal one's code (sgm_col_kernel), and only these shapes put few
+# rows, one column and the width limit to it.  The eight-path cases keep their ids.
 @pytest.mark.parametrize("cost", COSTS)
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
-def test_shapes(matcher, wide_matcher, case, cost):
+@pytest.mark.parametrize("case, paths", [
+    pytest.param(c, p, id="x".join(map(str, c)) + ("" if p == 8 else "-4paths")) for p in (8, 4) for c in CASES])
+def test_shapes(matcher, wide_matcher, case, paths, cost):
     W, H, D, r = case
-    L, R, ref = _case(case)
-    if case in DIFFERS_FROM_FOUR_PATHS:
-        four = PathsReference(_oracle(), L, R, r, D, paths=4).maps("sgm", cost)[0]
+    L, R, ref = _case(case, paths)
+    if paths == 8 and case in DIFFERS_FROM_FOUR_PATHS:
+        four = _case(case, 4)[2].maps("sgm", cost)[0]
         assert not np.array_equal(four, ref.maps("sgm", cost)[0]), "the case no longer tells 4 paths from 8"
-    _check(wide_matcher if W > WIDE else matcher, L, R, r, D, cost, ref, SUBPIX_COMBOS, f"{case} sgm+{cost}")
+    m = wide_matcher if W > WIDE else matcher
+    m.set_sgm_paths(paths)
+    try:
+        _check(m, L, R, r, D, cost, ref, SUBPIX_COMBOS, f"{case} sgm+{cost}, {paths} paths")
+    finally:
+        m.set_sgm_paths(8)
 
 
 # ---- 2. the 16-bit bound ----

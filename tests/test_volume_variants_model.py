@@ -24,7 +24,7 @@ PATHS8 = [("box", "census"), ("sgm", "ad"), ("sgm", "census")]   # box + ad is t
 PATHS16 = [("box", "ad")] + PATHS8                               # the sub-pixel calls keep a volume for it too
 
 # ---- the variant table: (W, H, D, r), the fuzz_pair seed, and what the launchers select for it ----
-# h: sgm_h_kernel<NJ, VEC>; v: sgm_v_kernel<DPT> with (d chunks, threads); cv: census_volume_kernel<VEC> with the rows
+# h: sgm_h_kernel<NJ, VEC>; v: sgm_col_kernel<DPT, DIAG> with (d chunks, threads); cv: census_volume_kernel<VEC> with the rows
 # per block that the width leaves; ad: ad_volume_kernel<KF>.  test_table_selects_what_it_says holds these to `select`.
 VARIANT_CASES = [
     # three registers per lane, scalar staging: lanes 0..42 are full (d = 128 is lane 42's third register), lane 43
@@ -247,7 +247,7 @@ def mutant_path(horizontal=None, vertical=None):
 
 
 LANE_CUT_H = mutant_path(horizontal=make_step(cut=3))      # sgm_h_kernel<3, *>: lane ends at d = 3k - 1 | 3k
-CHUNK_CUT_V = mutant_path(vertical=make_step(cut=8))       # sgm_v_kernel<8>: chunk ends at d = 8k - 1 | 8k
+CHUNK_CUT_V = mutant_path(vertical=make_step(cut=8))       # sgm_col_kernel<8, false>: chunk ends at d = 8k - 1 | 8k
 MOD_2_15 = mutant_path(make_step(post=lambda v: v % 32768), make_step(post=lambda v: v % 32768))
 SAT_65534 = mutant_path(make_step(post=lambda v: np.minimum(v, 65534)), make_step(post=lambda v: np.minimum(v, 65534)))
 
@@ -286,7 +286,7 @@ def test_table_selects_what_it_says():
 def test_every_compiled_variant_is_reached():
     """Restates launch_sgm_paths (bm_sgm.hip), launch_census_volume (bm_census.hip) and launch_ad_volume
     (bm_volume.hip) through `select`, and must be updated with them: the variant table together with the shapes of
-    the older tests reaches every sgm_h_kernel<NJ, VEC>, sgm_v_kernel<DPT>, census_volume_kernel<VEC> at one and two
+    the older tests reaches every sgm_h_kernel<NJ, VEC>, sgm_col_kernel<DPT, false>, census_volume_kernel<VEC> at one and two
     rows per block, and the two ad_volume_kernel<KF> that a width <= 4096 can select (KF = 4 needs 2 * nseg > 512)."""
     assert max(select(4096, h, 256)["ad"] for h in (1, 2, 8)) == 2
     shapes = [c[:3] for c, _, _ in VARIANT_CASES] + EXISTING_SHAPES
