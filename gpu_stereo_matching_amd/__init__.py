@@ -22,13 +22,13 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID, SM_AGG_SGM, SM_COST_CENSUS  # noqa: F401
+from ._capi import SMError, SM_AGG_BOX, SM_AGG_GUIDED, SM_LR_CHECK, SM_MEDIAN, SM_STAGED, SM_DEVICE_CU_GRID, SM_AGG_SGM, SM_COST_CENSUS, SM_PAIRS_IN_VIEW  # noqa: F401
 from .synth import synth_pair  # noqa: F401
 from .gray import bgr_to_gray  # noqa: F401
 
 __all__ = [
     "BlockMatcher", "BlockMatcherGroup", "blockMatching_gpu", "block_matching_gpu", "SMError", "synth_pair", "bgr_to_gray",
-    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_COST_CENSUS", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
+    "SM_AGG_BOX", "SM_AGG_GUIDED", "SM_AGG_SGM", "SM_COST_CENSUS", "SM_PAIRS_IN_VIEW", "SM_LR_CHECK", "SM_MEDIAN", "version", "host_empty",
     "sgm_penalties", "sgm_workspace_bytes", "census_workspace_bytes", "speckle_workspace_bytes", "to_float",
 ]
 
@@ -46,28 +46,36 @@ def _as_u8_image(a, name: str) -> np.ndarray:
     return a if a.flags.c_contiguous else np.ascontiguousarray(a)
 
 
-def _flags(agg: str, lr_check: bool, median: bool = False, cost: str = "ad") -> int:
+def _flags(agg: str, lr_check: bool, median: bool = False, cost: str = "ad", pairs: str = "reference") -> int:
     """cost: 'ad' (absolute gray difference) or 'census' (SM_COST_CENSUS: Hamming distance of 9 x 7 census words;
     agg 'box' or 'sgm', radius <= 7; the library rejects the other combinations with a reason).
     agg: 'box' (fused), 'box-staged' (through the AD / SAD volumes in HBM), 'guided', 'sgm' (four-path
     semi-global matching on the box SAD volume, radius <= 7), or 'device-cu' (Device.cu's literal output with
-    its fixed launch geometry: SM_DEVICE_CU_GRID, box only)."""
+    its fixed launch geometry: SM_DEVICE_CU_GRID, box only).
+    pairs: 'reference' (a pair (x, d) exists iff x + d <= W, the reference's rule) or 'in-view' (SM_PAIRS_IN_VIEW:
+    x - d >= 0, stereo geometry, with the handle's minimum disparity; the calls that keep a cost volume, i.e. agg
+    'sgm', cost 'census' and the sub-pixel calls; the library refuses it elsewhere with a reason)."""
     if agg not in ("box", "guided", "box-staged", "device-cu", "sgm"):
         raise ValueError("agg must be 'box', 'box-staged', 'guided', 'sgm' or 'device-cu'")
     if cost not in ("ad", "census"):
         raise ValueError("cost must be 'ad' or 'census'")
+    if pairs not in ("reference", "in-view"):
+        raise ValueError("pairs must be 'reference' or 'in-view'")
     f = {"box": SM_AGG_BOX, "guided": SM_AGG_GUIDED, "box-staged": SM_AGG_BOX | SM_STAGED,
          "device-cu": SM_DEVICE_CU_GRID, "sgm": SM_AGG_SGM}[agg]
-    return f | (SM_LR_CHECK if lr_check else 0) | (SM_MEDIAN if median else 0) | (SM_COST_CENSUS if cost == "census" else 0)
+    return f | (SM_LR_CHECK if lr_check else 0) | (SM_MEDIAN if median else 0) \
+        | (SM_COST_CENSUS if cost == "census" else 0) | (SM_PAIRS_IN_VIEW if pairs == "in-view" else 0)
 
 
-def sgm_penalties(radius: int, p1: int = 0, p2: int = 0, width: int = 1, cost: str = "ad") -> Tuple[int, int]:
+def sgm_penalties(radius: int, p1: int = 0, p2: int = 0, width: int = 1, cost: str = "ad",
+                  pairs: str = "reference") -> Tuple[int, int]:
     """The (P1, P2) an 'sgm' match at `radius` uses for the parameter values p1, p2 (0 = auto: 8 win^2 and
     32 win^2; with cost='census' 10 win^2 and 120 win^2), through the library's own argument check
     (sm_sgm_check, host-only); raises SMError where the match would (P1 > P2, 255 win^2 + P2 > 65535, or
     62 win^2 + P2 > 65535 with the census cost, radius > 7, width > 4096)."""
     a, b = ctypes.c_int(), ctypes.c_int()
-    _capi.check(_capi.load().sm_sgm_check(width, radius, _flags("sgm", False, False, cost), p1, p2, ctypes.byref(a),
+    _capi.check(_capi.load().sm_sgm_check(width, radius, _flags("sgm", False, False, cost, pairs), p1, p2,
+                                          ctypes.byref(a),
                                           ctypes.byref(b)))
     return a.value, b.value
 
@@ -200,6 +208,12 @@ class BlockMatcher:
         the penalties, their bound and the workspace are the same.  Other values raise SMError."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SGM_PATHS, float(paths)))
 
+    def set_min_disp(self, d0: int = 0):
+        """StereoSGBM's minDisparity for the pairs='in-view' calls (SM_PARAM_MIN_DISP): an integer 0..4095, default 0.
+        Those calls search d0 .. d0 + num_disp - 1 and return the absolute disparity (8-bit maps need
+        d0 + num_disp - 1 <= 255, the 1/16-px maps <= 4095).  With d0 > 0 every other matching call is refused."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_MIN_DISP, float(d0)))
+
     def set_box_kernel(self, kernel: int = 0):
         """Which kernel the plain box pass runs (SM_PARAM_BOX_KERNEL): 0 auto by launch size, 1 the VALU kernels,
         2 the matrix-pipe kernel, at every launch size; same maps and keys.  2 outside its scope (lr_check,
@@ -307,7 +321,7 @@ class BlockMatcher:
         return map_t
 
     def dslice_rehearse(self, left, right, radius: int, num_disp: int, members: int, agg: str = "box",
-                        lr_check: bool = False) -> np.ndarray:
+                        lr_check: bool = False, pairs: str = "reference") -> np.ndarray:
         """The d-slice split of BlockMatcherGroup.match_dslice with `members` members, run one after
         another on this device (sm_dslice_rehearse_u8): same slice plan, padding and finalisation, with
         the RCCL MIN reduce-scatter replaced by an elementwise MIN of the members' key maps.  lr_check:
@@ -321,15 +335,18 @@ class BlockMatcher:
         H, W = L.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_dslice_rehearse_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
-                                                    _flags(agg, lr_check, False), members, out.ctypes.data, W))
+                                                    _flags(agg, lr_check, False, pairs=pairs), members,
+                                                    out.ctypes.data, W))
         return out
 
     # -- host-pointer path (blockMatching_gpu replacement) -------------------------------
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-              median: bool = False, out: Optional[np.ndarray] = None, cost: str = "ad") -> np.ndarray:
+              median: bool = False, out: Optional[np.ndarray] = None, cost: str = "ad",
+              pairs: str = "reference") -> np.ndarray:
         """median=True: 7x7 median of the WTA map(s) (STMatching MeanFilter(disp, disp, 3)), before the LR check.
         out: optional contiguous uint8 [H, W] host buffer (e.g. pinned memory) to write the map into.
-        cost: 'ad' or 'census' (SM_COST_CENSUS, with agg 'box' or 'sgm')."""
+        cost: 'ad' or 'census' (SM_COST_CENSUS, with agg 'box' or 'sgm').
+        pairs: 'reference' or 'in-view' (SM_PAIRS_IN_VIEW, with agg 'sgm' or cost 'census'; see set_min_disp)."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
         if L.shape != R.shape:
@@ -340,11 +357,11 @@ class BlockMatcher:
         elif out.dtype != np.uint8 or out.shape != (H, W) or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous uint8 array of the frame's shape")
         _capi.check(self._lib.sm_block_match_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
-                                                _flags(agg, lr_check, median, cost), out.ctypes.data, W))
+                                                _flags(agg, lr_check, median, cost, pairs), out.ctypes.data, W))
         return out
 
     def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False,
-                 cost: str = "ad") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                 cost: str = "ad", pairs: str = "reference") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(checked disparity, right-view disparity, valid mask)."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
@@ -353,12 +370,13 @@ class BlockMatcher:
         rd = np.empty((H, W), np.uint8)
         mask = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_block_match_lr_u8(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
-                                                   _flags(agg, True, median, cost), out.ctypes.data, rd.ctypes.data,
+                                                   _flags(agg, True, median, cost, pairs), out.ctypes.data,
+                                                   rd.ctypes.data,
                                                    mask.ctypes.data, W))
         return out, rd, mask
 
     def match_bgr(self, left_bgr, right_bgr, radius: int, num_disp: int, agg: str = "box",
-                  lr_check: bool = False, cost: str = "ad") -> np.ndarray:
+                  lr_check: bool = False, cost: str = "ad", pairs: str = "reference") -> np.ndarray:
         """imread -> cvtColor(BGR2GRAY) -> blockMatching_gpu in one call (Caller.cpp:12-19): HxWx3/4
         uint8 BGR(A) frames in, uint8 disparity out; the gray conversion runs on the GPU."""
         Lb = np.ascontiguousarray(left_bgr, dtype=np.uint8)
@@ -368,7 +386,8 @@ class BlockMatcher:
         H, W, C = Lb.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_block_match_bgr_u8(self._h, Lb.ctypes.data, Rb.ctypes.data, W, H, W * C, C, radius,
-                                                    num_disp, _flags(agg, lr_check, False, cost), out.ctypes.data, W))
+                                                    num_disp, _flags(agg, lr_check, False, cost, pairs),
+                                                    out.ctypes.data, W))
         return out
 
     def segment_tree(self, left_bgr, right_bgr, max_level: int = 60, scale: int = 4, sigma: float = 0.1,
@@ -632,7 +651,8 @@ class BlockMatcher:
         return ctypes.c_void_p(stream.cuda_stream)
 
     def match_device(self, left_t, right_t, radius: int, num_disp: int, out_t=None, agg: str = "box",
-                     lr_check: bool = False, stream=None, median: bool = False, cost: str = "ad"):
+                     lr_check: bool = False, stream=None, median: bool = False, cost: str = "ad",
+                     pairs: str = "reference"):
         """left_t/right_t: uint8 cuda tensors [H, W] or [B, H, W] (contiguous). Async on `stream`.
         cost='census': the frames of a batch run one after another through the handle's volume workspace."""
         import torch
@@ -650,7 +670,8 @@ class BlockMatcher:
             out_t = torch.empty_like(left_t)
         _check_out(out_t, left_t.shape, torch.uint8, left_t.device)
         _capi.check(self._lib.sm_match_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, W, B, H * W,
-                                              radius, num_disp, _flags(agg, lr_check, median, cost), out_t.data_ptr(), W,
+                                              radius, num_disp, _flags(agg, lr_check, median, cost, pairs),
+                                              out_t.data_ptr(), W,
                                               H * W, self._stream_ptr(stream)))
         return out_t
 
@@ -661,10 +682,12 @@ class BlockMatcher:
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_UNIQUENESS, float(u)))
 
     def match_subpix(self, left, right, radius: int, num_disp: int, agg: str = "sgm", cost: str = "ad",
-                     lr_check: bool = False, return_right: bool = False, return_mask: bool = False):
+                     lr_check: bool = False, return_right: bool = False, return_mask: bool = False,
+                     pairs: str = "reference"):
         """uint16 [H, W] disparity in 1/16 px (sm_block_match_subpix_u16): 16 * d + a parabola fit through the
         costs next to the best d, 0 where the pixel is invalid (uniqueness, the AD box threshold) or occluded
-        (lr_check).  agg 'box' or 'sgm', cost 'ad' or 'census', radius <= 7.  return_right / return_mask: a tuple
+        (lr_check).  agg 'box' or 'sgm', cost 'ad' or 'census', radius <= 7.  pairs='in-view': SM_PAIRS_IN_VIEW with
+        the handle's minimum disparity, values up to 16 * 4095 + 8.  return_right / return_mask: a tuple
         (map[, right-view map][, uint8 valid mask])."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
@@ -675,13 +698,15 @@ class BlockMatcher:
         rd = np.empty((H, W), np.uint16) if return_right else None
         mask = np.empty((H, W), np.uint8) if return_mask else None
         _capi.check(self._lib.sm_block_match_subpix_u16(
-            self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp, _flags(agg, lr_check, False, cost),
-            out.ctypes.data, rd.ctypes.data if return_right else None, mask.ctypes.data if return_mask else None, W))
+            self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
+            _flags(agg, lr_check, False, cost, pairs), out.ctypes.data, rd.ctypes.data if return_right else None,
+            mask.ctypes.data if return_mask else None, W))
         res = (out,) + ((rd,) if return_right else ()) + ((mask,) if return_mask else ())
         return res[0] if len(res) == 1 else res
 
     def match_subpix_device(self, left_t, right_t, radius: int, num_disp: int, out_t=None, agg: str = "sgm",
-                            cost: str = "ad", lr_check: bool = False, right_t16=None, mask_t=None, stream=None):
+                            cost: str = "ad", lr_check: bool = False, right_t16=None, mask_t=None, stream=None,
+                            pairs: str = "reference"):
         """Device form of :meth:`match_subpix` (sm_match_subpix_device), async on `stream`.  left_t / right_t: uint8
         cuda tensors [H, W] or [B, H, W] of one layout whose rows are contiguous (row and frame strides are passed
         on).  The map comes back as an int16 tensor holding the uint16 bit patterns (at most 4088, so the values
@@ -711,16 +736,17 @@ class BlockMatcher:
         ofs = out_t.stride(0) if out_t.dim() == 3 else out_t.stride(-2) * H
         _capi.check(self._lib.sm_match_subpix_device(
             self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, left_t.stride(-2), B, fs, radius, num_disp,
-            _flags(agg, lr_check, False, cost), out_t.data_ptr(), out_t.stride(-2), ofs,
+            _flags(agg, lr_check, False, cost, pairs), out_t.data_ptr(), out_t.stride(-2), ofs,
             right_t16.data_ptr() if right_t16 is not None else None,
             mask_t.data_ptr() if mask_t is not None else None, self._stream_ptr(stream)))
         return out_t
 
     def volume_wta_subpix_device(self, vol_t, invalid_from: int = 0, lr_check: bool = False, out_t=None,
-                                 right_t16=None, mask_t=None, stream=None):
+                                 right_t16=None, mask_t=None, stream=None, pairs: str = "reference"):
         """The sub-pixel WTA on a caller's cost volume (sm_volume_wta_subpix_device): vol_t a contiguous
         [D, H, W] cuda tensor of int16 (uint16 bit patterns) or int32 (uint32, costs < 2^24); the left view is
         invalid where its best cost is >= invalid_from (0 = no threshold); the handle's uniqueness applies.
+        pairs='in-view': plane k of vol_t is the disparity set_min_disp's d0 + k, under SM_PAIRS_IN_VIEW.
         Returns the int16 [H, W] map (uint16 bit patterns)."""
         import torch
         if vol_t.dtype not in (torch.int16, torch.int32) or vol_t.dim() != 3 or not vol_t.is_cuda \
@@ -736,7 +762,7 @@ class BlockMatcher:
             _check_out(mask_t, (H, W), torch.uint8, vol_t.device, "mask_t")
         _capi.check(self._lib.sm_volume_wta_subpix_device(
             self._h, vol_t.data_ptr(), vol_t.element_size(), W, H, D, int(invalid_from),
-            SM_LR_CHECK if lr_check else 0, out_t.data_ptr(), W,
+            _flags("box", lr_check, pairs=pairs), out_t.data_ptr(), W,
             right_t16.data_ptr() if right_t16 is not None else None,
             mask_t.data_ptr() if mask_t is not None else None, self._stream_ptr(stream)))
         return out_t
@@ -806,7 +832,7 @@ class BlockMatcher:
         return keys_t
 
     def slice_keys_lr_device(self, left_t, right_t, radius: int, d_lo: int, d_hi: int, agg: str = "box",
-                             keys_t=None, right_keys_t=None, stream=None):
+                             keys_t=None, right_keys_t=None, stream=None, pairs: str = "reference"):
         """Left AND right-view d-slice keys of [d_lo, d_hi) from one fused pass (sm_slice_keys_lr_device): int32
         [H, W] tensors holding the bit patterns of box uint32 keys (combine with an unsigned MIN) or guided
         int32 keys (signed MIN).  The right view's key of u is its best (cost << 8 | d) over the slice's d with
@@ -822,7 +848,7 @@ class BlockMatcher:
         _check_device_pair(left_t, right_t, keys_t)
         _check_device_pair(left_t, right_t, right_keys_t)
         _capi.check(self._lib.sm_slice_keys_lr_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H, W, radius,
-                                                      d_lo, d_hi, _flags(agg, False), keys_t.data_ptr(),
+                                                      d_lo, d_hi, _flags(agg, False, pairs=pairs), keys_t.data_ptr(),
                                                       right_keys_t.data_ptr(), self._stream_ptr(stream)))
         return keys_t, right_keys_t
 
@@ -916,6 +942,10 @@ class BlockMatcherGroup:
         """BlockMatcher.set_sgm_paths on every member (agg='sgm' runs in match_batch only: whole frames)."""
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_SGM_PATHS, float(paths)))
 
+    def set_min_disp(self, d0: int = 0):
+        """BlockMatcher.set_min_disp on every member (match_batch with pairs='in-view' honours it)."""
+        _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_MIN_DISP, float(d0)))
+
     def set_speckle(self, size: int = 0, range: int = 1):  # noqa: A002
         """BlockMatcher.set_speckle on every member: match_batch runs whole frames and honours it; the row-band
         calls (match, match_lr) and match_dslice refuse a size > 0 and say why."""
@@ -928,7 +958,7 @@ class BlockMatcherGroup:
         _capi.check(self._lib.sm_group_set_param_f(self._g, _capi.SM_PARAM_FILL_GAP, float(int(max_gap))))
 
     def match(self, left, right, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-              median: bool = False, cost: str = "ad") -> np.ndarray:
+              median: bool = False, cost: str = "ad", pairs: str = "reference") -> np.ndarray:
         """One frame, row-banded over the group (sm_group_block_match_u8).  cost='census' needs whole frames
         (match_batch): the library refuses it here and says why."""
         L = _as_u8_image(left, "left")
@@ -938,23 +968,24 @@ class BlockMatcherGroup:
         H, W = L.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_group_block_match_u8(self._g, L.ctypes.data, R.ctypes.data, W, H, W, radius,
-                                                      num_disp, _flags(agg, lr_check, median, cost), out.ctypes.data, W))
+                                                      num_disp, _flags(agg, lr_check, median, cost, pairs),
+                                                      out.ctypes.data, W))
         return out
 
-    def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False
-                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def match_lr(self, left, right, radius: int, num_disp: int, agg: str = "box", median: bool = False,
+                 pairs: str = "reference") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(checked disparity, right-view disparity, valid mask), row-banded over the group."""
         L = _as_u8_image(left, "left")
         R = _as_u8_image(right, "right")
         H, W = L.shape
         out, rd, mask = (np.empty((H, W), np.uint8) for _ in range(3))
         _capi.check(self._lib.sm_group_block_match_lr_u8(self._g, L.ctypes.data, R.ctypes.data, W, H, W, radius,
-                                                         num_disp, _flags(agg, True, median), out.ctypes.data,
+                                                         num_disp, _flags(agg, True, median, pairs=pairs), out.ctypes.data,
                                                          rd.ctypes.data, mask.ctypes.data, W))
         return out, rd, mask
 
     def match_dslice(self, left, right, radius: int, num_disp: int, agg: str = "box",
-                     lr_check: bool = False) -> np.ndarray:
+                     lr_check: bool = False, pairs: str = "reference") -> np.ndarray:
         """One frame sharded over disparities (sm_group_dslice_block_match_u8): each member matches
         its slice of [0, num_disp), RCCL MIN reduce-scatter + all-gather over the members' devices.
         lr_check: the right view's slice keys take a second reduce-scatter + all-gather and the map is
@@ -968,11 +999,12 @@ class BlockMatcherGroup:
         H, W = L.shape
         out = np.empty((H, W), np.uint8)
         _capi.check(self._lib.sm_group_dslice_block_match_u8(self._g, L.ctypes.data, R.ctypes.data, W, H, W, radius,
-                                                             num_disp, _flags(agg, lr_check, False), out.ctypes.data, W))
+                                                             num_disp, _flags(agg, lr_check, False, pairs=pairs),
+                                                             out.ctypes.data, W))
         return out
 
     def match_batch(self, lefts, rights, radius: int, num_disp: int, agg: str = "box", lr_check: bool = False,
-                    median: bool = False, cost: str = "ad"):
+                    median: bool = False, cost: str = "ad", pairs: str = "reference"):
         """A list of equal-size pairs; frame f runs on member f mod len(group)."""
         Ls = [_as_u8_image(a, "left") for a in lefts]
         Rs = [_as_u8_image(a, "right") for a in rights]
@@ -985,7 +1017,8 @@ class BlockMatcherGroup:
         n = len(Ls)
         ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
         _capi.check(self._lib.sm_group_block_match_batch_u8(self._g, ptrs(Ls), ptrs(Rs), n, W, H, W, radius,
-                                                            num_disp, _flags(agg, lr_check, median, cost), ptrs(outs), W))
+                                                            num_disp, _flags(agg, lr_check, median, cost, pairs),
+                                                            ptrs(outs), W))
         return outs
 
 

@@ -26,6 +26,7 @@ SM_STAGED = 8
 SM_DEVICE_CU_GRID = 16
 SM_AGG_SGM = 32
 SM_COST_CENSUS = 64
+SM_PAIRS_IN_VIEW = 128
 
 SM_PARAM_GUIDED_EPS = 1
 SM_PARAM_STAGED_GROUP = 2
@@ -40,6 +41,7 @@ SM_PARAM_SPECKLE_RANGE = 10
 SM_PARAM_FILL_GAP = 11
 SM_PARAM_BOX_QUEUE_WORKGROUPS = 12
 SM_PARAM_SGM_PATHS = 13
+SM_PARAM_MIN_DISP = 14
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (

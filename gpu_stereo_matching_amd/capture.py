@@ -77,7 +77,7 @@ def _write_png(path: str, disp: np.ndarray) -> None:
 
 def run_loop(source, matcher, radius: int = 5, num_disp: int = 64, rectify_maps=None, batch: int = 4,
              agg: str = "box", on_map: Optional[Callable[[int, np.ndarray], None]] = None,
-             out_dir: Optional[str] = None, cost: str = "ad") -> List[int]:
+             out_dir: Optional[str] = None, cost: str = "ad", pairs: str = "reference") -> List[int]:
     """Match every pair of `source` (an iterable of ``(n, left_bgr, right_bgr)``, e.g. a PairSequence),
     `batch` pairs per GPU launch through FrameStream (BGR -> gray -> [rectify] -> match on the GPU).
     Returns the pair numbers in the order their maps were delivered (the input order).  A short last
@@ -107,7 +107,7 @@ def run_loop(source, matcher, radius: int = 5, num_disp: int = 64, rectify_maps=
         H, W = ls[0].shape[:2]
         if fs is None:
             fs = FrameStream(matcher, batch, W, H, radius, num_disp, agg=agg, bgr=True, rectify_maps=rectify_maps,
-                             cost=cost)
+                             cost=cost, pairs=pairs)
         elif (fs.H, fs.W) != (H, W):
             raise ValueError(f"pair {ns[0]}: frame size {W}x{H} differs from the stream's {fs.W}x{fs.H}")
         while len(ls) < batch:
@@ -148,6 +148,11 @@ def _main(argv=None) -> int:
                     help="matching cost: absolute difference, or census / Hamming (with --agg box or sgm, radius <= 7)")
     ap.add_argument("--sgm-paths", type=int, default=4, choices=[4, 8],
                     help="scan directions of --agg sgm: 4, or 8 with the diagonals (four more path passes)")
+    ap.add_argument("--pairs", dest="pair_rule", default="reference", choices=["reference", "in-view"],
+                    help="which (x, d) are candidates: the reference's x + d <= W, or in-view, x - d >= 0 "
+                         "(SM_PAIRS_IN_VIEW; with --agg sgm or --cost census)")
+    ap.add_argument("--min-disp", type=int, default=0,
+                    help="with --pairs in-view: search --min-disp .. --min-disp + --disp - 1 (SM_PARAM_MIN_DISP)")
     ap.add_argument("--out", help="directory for disp_<n>.png")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -162,8 +167,10 @@ def _main(argv=None) -> int:
     H, W = first[1].shape[:2]
     with BlockMatcher(a.device, W, H, max(a.disp, 1)) as m:
         m.set_sgm_paths(a.sgm_paths)
+        m.set_min_disp(a.min_disp)
         maps = calib.rectify(m, *calib.load_data_batch(a.calib), (W, H)) if a.calib else None
         done = run_loop(seq, m, a.radius, a.disp, rectify_maps=maps, batch=a.batch, agg=a.agg, out_dir=a.out, cost=a.cost,
+                        pairs=a.pair_rule,
                         on_map=lambda n, d: print(f"pair {n}: {W}x{H}, {int((d > 0).sum())} matched pixels"))
     print(f"{len(done)} pairs matched")
     return 0

@@ -125,9 +125,12 @@ __global__ __launch_bounds__(256) void min_keys_u32_kernel(uint32_t* __restrict_
 }
 
 __global__ __launch_bounds__(256) void keys_low_byte_kernel(const uint32_t* __restrict__ keys, int64_t n,
-                                                            uint8_t* __restrict__ out) {
+                                                            uint8_t* __restrict__ out, int in_view, int d0) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (uint8_t)(keys[i] & 0xFFu);
+    if (i >= n) return;
+    const uint32_t k = keys[i];
+    // SM_PAIRS_IN_VIEW: the low byte is the plane, d = d0 + k, and an untouched key (no pair reached the pixel) is 0
+    out[i] = in_view && k == 0xFFFFFFFFu ? (uint8_t)0 : (uint8_t)((k & 0xFFu) + (uint32_t)d0);
 }
 
 }  // namespace
@@ -138,9 +141,11 @@ hipError_t launch_min_keys_u32(uint32_t* acc, const uint32_t* src, int64_t n, hi
     return hipGetLastError();
 }
 
-hipError_t launch_keys_low_byte(const uint32_t* keys, int64_t n, uint8_t* out, hipStream_t s) {
+hipError_t launch_keys_low_byte(const uint32_t* keys, int64_t n, uint8_t* out, hipStream_t s, int in_view, int d0) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(keys_low_byte_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, n, out);
+    if (d0 < 0 || d0 > 255 || (d0 && !in_view)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_low_byte_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, n, out, in_view,
+                       d0);
     return hipGetLastError();
 }
 

@@ -67,6 +67,9 @@ __global__ __launch_bounds__(256) void census_kernel(const uint8_t* __restrict__
 // padding, which spreads the 32 lanes of a ds_read_b64 group over all 64 banks (128-B strides would put them on two).
 // With RB * nseg segments per block: 256 / (RB * nseg) groups of threads each walk a contiguous share of the
 // chunk's disparities.  Bytes at x < d are 0, as the AD volume's.
+// d0 (SM_PARAM_MIN_DISP, the matching calls with SM_PAIRS_IN_VIEW alone; the public volume calls pass 0): plane k holds
+// the disparity d0 + k, which is plane k of the d0 = 0 volume of a frame whose columns are numbered from -d0: the ring
+// and the masks take the segment's first column as xr = x0 - d0 and nothing else changes.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kHT = 256;
 constexpr int kHSeg = 16;
@@ -76,10 +79,12 @@ constexpr int kHamSplit = 2;
 
 __host__ __device__ __forceinline__ int lds_word(int x) { return x + (x >> 4); }
 
+// Four waves per SIMD, 128 VGPRs, is what the VEC form compiled to before xr; with it the allocator stops at 130,
+// a fifth granule and three waves, unless it is told the target (no scratch either way)
 template <bool VEC>
-__global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __restrict__ cL,
+__global__ __launch_bounds__(kHT) __attribute__((amdgpu_waves_per_eu(4))) void census_volume_kernel(const uint64_t* __restrict__ cL,
                                                             const uint64_t* __restrict__ cR, int W, int H, int D,
-                                                            int RB, int dsp, uint8_t* __restrict__ ham) {
+                                                            int RB, int dsp, int d0, uint8_t* __restrict__ ham) {
     extern __shared__ __attribute__((aligned(16))) uint64_t rrow[];   // [RB][rstride]
     const int y0 = blockIdx.x * RB;
     const int dc = (D + dsp - 1) / dsp;
@@ -101,6 +106,7 @@ __global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __re
     const int dg = (d_end - d_begin + groups - 1) / groups;
     const int lo = d_begin + g * dg, hi = min(d_end, lo + dg);
     if (lo >= hi) return;
+    const int xr = x0 - d0;                              // the segment's first column as the right image sees it
     const int y = y0 + i;
     const int n = min(kHSeg, W - x0);                    // columns of this segment inside the row
     uint64_t l[kHSeg], w[kHSeg];
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __re
     for (int k = 0; k < kHSeg; ++k) {
         l[k] = k < n ? lrow[k] : 0ull;
         // columns left of d (masked below) and right of the row (never stored) read a clamped word
-        w[k] = rr[lds_word(min(max(x0 + k - lo, 0), W - 1))];
+        w[k] = rr[lds_word(min(max(xr + k - lo, 0), W - 1))];
     }
     const int64_t P = (int64_t)W * H;
     uint8_t* dst = ham + (int64_t)lo * P + (int64_t)y * W + x0;   // this segment in plane d, from d = lo on
@@ -127,10 +133,10 @@ __global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __re
             }
             o[q] = v;
         }
-        if (x0 < d) {   // dword q drops its low clamp(d - x0 - 4q, 0, 4) bytes
+        if (xr < d) {   // dword q drops its low clamp(d - xr - 4q, 0, 4) bytes
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int nz = min(max(d - x0 - 4 * q, 0), 4);
+                const int nz = min(max(d - xr - 4 * q, 0), 4);
                 o[q] &= (uint32_t)(~0ull << (8 * nz));
             }
         }
@@ -152,7 +158,7 @@ __global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __re
 #pragma unroll
         for (int j = 0; j < kHSeg; ++j) {
             const int d = db + j;
-            if (j > 0 || db > lo) w[(kHSeg - j) & (kHSeg - 1)] = rr[lds_word(max(x0 - d, 0))];
+            if (j > 0 || db > lo) w[(kHSeg - j) & (kHSeg - 1)] = rr[lds_word(max(xr - d, 0))];
             emit(d, j);
         }
     }
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(kHT) void census_volume_kernel(const uint64_t* __re
 #pragma unroll
             for (int k = kHSeg - 1; k > 0; --k) w[k] = w[k - 1];
         }
-        if (d > lo) w[0] = rr[lds_word(max(x0 - d, 0))];
+        if (d > lo) w[0] = rr[lds_word(max(xr - d, 0))];
         emit(d, 0);
     }
 }
@@ -179,8 +185,9 @@ hipError_t launch_census(const uint8_t* img, int W, int H, int pitch, uint64_t* 
 }
 
 hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, int H, int D, uint8_t* ham,
-                                hipStream_t s) {
-    if (!cL || !cR || !ham || W <= 0 || W > 4096 || H <= 0 || D < 1 || D > kMaxDisp) return hipErrorInvalidValue;
+                                hipStream_t s, int d0) {
+    if (!cL || !cR || !ham || W <= 0 || W > 4096 || H <= 0 || D < 1 || D > kMaxDisp || d0 < 0 || d0 > 4095)
+        return hipErrorInvalidValue;
     const int nseg = (W + kHSeg - 1) / kHSeg;            // <= 256 = kHT
     int rb = 2 * nseg <= kHT ? 2 : 1;
     if (rb > H) rb = H;
@@ -189,9 +196,9 @@ hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, i
     const dim3 grid((unsigned)((H + rb - 1) / rb), (unsigned)dsplit);
     const bool vec = W % kHSeg == 0 && (reinterpret_cast<uintptr_t>(ham) & 15) == 0;
     if (vec)
-        hipLaunchKernelGGL(census_volume_kernel<true>, grid, dim3(kHT), lds, s, cL, cR, W, H, D, rb, dsplit, ham);
+        hipLaunchKernelGGL(census_volume_kernel<true>, grid, dim3(kHT), lds, s, cL, cR, W, H, D, rb, dsplit, d0, ham);
     else
-        hipLaunchKernelGGL(census_volume_kernel<false>, grid, dim3(kHT), lds, s, cL, cR, W, H, D, rb, dsplit, ham);
+        hipLaunchKernelGGL(census_volume_kernel<false>, grid, dim3(kHT), lds, s, cL, cR, W, H, D, rb, dsplit, d0, ham);
     return hipGetLastError();
 }
 

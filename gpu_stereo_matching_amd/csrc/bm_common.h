@@ -35,6 +35,20 @@ inline BoxGeom box_geom(const MatchArgs& a, int batch) {
     return BoxGeom{a.W, a.H, a.pitch, a.radius, a.d_lo, a.d_hi, batch};
 }
 
+// Which pairs (x, k) of a d-major cost volume exist, plane k standing for the disparity d = d0 + k, k = 0 .. D - 1.
+// At every column they are a prefix of the planes, k <= min(D - 1, ka + kb * x):
+//   the reference's rule (Device.cu:44)   x + d <= W,  d0 = 0:   (ka, kb) = (W, -1)
+//   SM_PAIRS_IN_VIEW                      x - d >= 0:            (ka, kb) = (-d0, +1), negative where x < d0
+// The kernels take (ka, kb) as arguments, so both rules run the same code.
+struct Pairs {
+    int in_view = 0;   // SM_PAIRS_IN_VIEW
+    int d0 = 0;        // SM_PARAM_MIN_DISP; 0 unless in_view
+    int ka(int W) const { return in_view ? -d0 : W; }
+    int kb() const { return in_view ? 1 : -1; }
+    // what a launcher takes: the largest disparity d0 + D - 1 fits the map (255 or 4095)
+    bool ok(int D, int d_limit) const { return d0 >= 0 && (in_view ? d0 + D - 1 <= d_limit : d0 == 0); }
+};
+
 // The CU count of the current device, asked once per device index: the handles of a group on several devices size
 // each launch by their own device (256 when the query fails).
 inline int device_cus() {
@@ -144,8 +158,11 @@ hipError_t launch_box_match_lr(const MatchArgs& a, int batch, int check, uint8_t
 hipError_t launch_box_slice_lr_keys(const MatchArgs& a, int batch, uint32_t* right_keys, hipStream_t s);
 // acc = min(acc, src) elementwise over n unsigned keys
 hipError_t launch_min_keys_u32(uint32_t* acc, const uint32_t* src, int64_t n, hipStream_t s);
-// right-view key map -> dR: the d field (low byte) of each key, no threshold (StereoHelper.cpp:131-154)
-hipError_t launch_keys_low_byte(const uint32_t* keys, int64_t n, uint8_t* out, hipStream_t s);
+// right-view key map -> dR: the d field (low byte) of each key, no threshold (StereoHelper.cpp:131-154).
+// in_view (SM_PAIRS_IN_VIEW): the low byte is the plane k, dR = d0 + k, and the key ~0 of a pixel no pair reached
+// gives 0, never its low byte
+hipError_t launch_keys_low_byte(const uint32_t* keys, int64_t n, uint8_t* out, hipStream_t s, int in_view = 0,
+                                int d0 = 0);
 hipError_t launch_keys_to_disp(const uint32_t* keys, int W, int H, uint32_t thresh_key,
                                uint8_t* disp, int out_pitch, hipStream_t s);
 // acc = min(acc, src) elementwise over n signed keys (the d-slice MIN, rehearsed on one device)
@@ -158,9 +175,10 @@ hipError_t launch_lr_check(const uint8_t* left_disp, int lpitch, int64_t lstride
                            int W, int H, int batch, uint8_t* out, int opitch, int64_t ostride,
                            uint8_t* right_out, uint8_t* mask_out, int aux_pitch, int64_t aux_stride,
                            hipStream_t s);
-// AD volume dif[d][y][x] (PreCal / kernalPreCal_V2), d-major planes per frame (bm_volume.hip)
+// AD volume dif[d][y][x] (PreCal / kernalPreCal_V2), d-major planes per frame (bm_volume.hip).  d0
+// (SM_PARAM_MIN_DISP, the matching calls alone): plane k holds |L(y, x) - R(y, x - d0 - k)|, 0 for x < d0 + k
 hipError_t launch_ad_volume(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int64_t fstride, int batch,
-                            int D, uint8_t* dif, int64_t dstride, hipStream_t s);
+                            int D, uint8_t* dif, int64_t dstride, hipStream_t s, int d0 = 0);
 // staged box path (bm_staged.hip): u16 SAD volume from the AD volume, and WTA over the SAD volume
 // `ad` must have 8 readable bytes past its last plane (the handle's volume buffer carries that slack, sm_handle.h)
 hipError_t launch_box_sad_volume(const uint8_t* ad, int W, int H, int radius, int D, uint16_t* sad, hipStream_t s);
@@ -199,24 +217,28 @@ hipError_t launch_device_cu_literal(const uint8_t* L, const uint8_t* R, int W, i
 // volume (0 <= P1 <= P2, 255 * win^2 + P2 <= 65535; paths: 4, or 8 with the diagonals), and the WTA over it: the left map (smallest existing d at
 // min S, no threshold) and, when right_keys is given, the right view's keys [H][W], min over the d whose pair
 // (u + d, d) exists of (S(u + d, d) << 8 | d)
-hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, uint32_t* S,
-                            hipStream_t s);
-hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
-                          hipStream_t s);
+// pr: which pairs exist (Pairs, above); with pr.in_view the maps hold d0 + k and a pixel with no candidate 0
+hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, const Pairs& pr,
+                            uint32_t* S, hipStream_t s);
+hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, const Pairs& pr, uint8_t* disp, int out_pitch,
+                          uint32_t* right_keys, hipStream_t s);
 // the same WTA, thresholdless, over a u16 cost volume [D][H][W] (SM_COST_CENSUS with SM_AGG_BOX)
-hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, uint8_t* disp, int out_pitch,
+hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, const Pairs& pr, uint8_t* disp, int out_pitch,
                                uint32_t* right_keys, hipStream_t s);
 // sub-pixel WTA (bm_subpix.hip) over a d-major volume [D][H][W] of costs < 2^24: disp16 [H][pitch] receives
 // q = 16 d0 + delta (1/16 px), right16 (optional, dense) the right view's q, mask (optional, dense) the validity.
 // invalid_from: 0, or the left view is invalid where its minimum is >= it; uniq 0..99: the uniqueness ratio (0 off);
 // right_pairs: 1 the right view over u + 2 d <= W, 2 over u + d < W; lr: the LR check on the two views' d0, through
 // `scratch` (2 W H bytes).  Invalid and occluded pixels get q = 0, mask = 0.
+// pr.in_view (SM_PAIRS_IN_VIEW): plane k is d = pr.d0 + k, q = 16 (d0 + k0) + delta up to 16 * 4095 + 8; the left view
+// over x - d >= 0, the right view V_R(u, k) = V(u + d0 + k, k) over u + d0 + k <= W - 1 whatever right_pairs says; a
+// pixel with no candidate is invalid; the views' disparities of the check are 16-bit, `scratch` 4 W H bytes.
 hipError_t launch_subpix_wta_u32(const uint32_t* vol, int W, int H, int D, uint32_t invalid_from, int uniq,
                                  int right_pairs, bool lr, uint16_t* disp16, int pitch, uint16_t* right16,
-                                 uint8_t* mask, uint8_t* scratch, hipStream_t s);
+                                 uint8_t* mask, uint8_t* scratch, hipStream_t s, const Pairs& pr = Pairs());
 hipError_t launch_subpix_wta_u16(const uint16_t* vol, int W, int H, int D, uint32_t invalid_from, int uniq,
                                  int right_pairs, bool lr, uint16_t* disp16, int pitch, uint16_t* right16,
-                                 uint8_t* mask, uint8_t* scratch, hipStream_t s);
+                                 uint8_t* mask, uint8_t* scratch, hipStream_t s, const Pairs& pr = Pairs());
 // 1/16-px map -> points: xyz [H][xyz_pitch] floats, (X, Y, Z) / w of Q (x, y, q / 16, 1) (Q row-major 4 x 4),
 // (0, 0, 0) where q == 0 or w == 0
 hipError_t launch_reproject(const uint16_t* disp16, int W, int H, int pitch, const double* Q, float* xyz,
@@ -225,8 +247,9 @@ hipError_t launch_reproject(const uint16_t* disp16, int W, int H, int pitch, con
 // the Hamming volume u8 [D][H][W] of two census images, popcount(cL(y, x) ^ cR(y, x - d)) for x >= d, else 0:
 // the AD volume's layout, so launch_box_sad_volume sums it (<= 62 * win^2); W <= 4096
 hipError_t launch_census(const uint8_t* img, int W, int H, int pitch, uint64_t* census, hipStream_t s);
+// d0 (SM_PARAM_MIN_DISP, the matching calls alone): plane k compares cL(y, x) with cR(y, x - d0 - k), 0 for x < d0 + k
 hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, int H, int D, uint8_t* ham,
-                                hipStream_t s);
+                                hipStream_t s, int d0 = 0);
 // (2r+1)^2 median with replicate borders, radius 1..3 (bm_post.hip)
 hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
                          uint8_t* dst, int dpitch, int64_t dstride, hipStream_t s);

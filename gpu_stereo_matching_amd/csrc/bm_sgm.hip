@@ -4,12 +4,19 @@
 // The recursion of one path direction rho, with q = p - rho the previous pixel on the path:
 //     L(p, d) = C(p, d)                                                              q outside the image
 //     L(p, d) = C(p, d) + min(L(q, d), L(q, d-1) + P1, L(q, d+1) + P1, M + P2) - M   M = min_k L(q, k)
-// over the pairs (x, d) that exist (x + d <= W, Device.cu:44).  A pair that does not exist is carried as
-// kInf, which loses every min, so the "dropped terms" of the definition need no branches.  L <= C + P2 fits
-// u16 (the entry points check 255 * win^2 + P2 <= 65535); the sum S of the four directions (+-1, 0), (0, +-1), and
+// over the pairs (x, d) that exist (x + d <= W, Device.cu:44; with SM_PAIRS_IN_VIEW x - d >= 0, below).  A pair that
+// does not exist is carried as kInf, which loses every min, so the "dropped terms" of the definition need no
+// branches.  L <= C + P2 fits u16 (the entry points check 255 * win^2 + P2 <= 65535); the sum S of the four
+// directions (+-1, 0), (0, +-1), and
 // with SM_PARAM_SGM_PATHS 8 of the four diagonals (+-1, +-1) too, is u32 [D][H][W] (< 2^18, with eight < 2^19),
 // zeroed by the caller and accumulated with no-return global atomic adds, so the directions need no
 // order among themselves and integer addition keeps the sum exact.
+//
+// Which pairs exist is a prefix of the planes at every column, k <= dmax(x) = min(D - 1, ka + kb * x): the kernels
+// take (ka, kb) as arguments, (W, -1) for the reference's rule and (-d0, +1) for SM_PAIRS_IN_VIEW, where plane k
+// stands for d = d0 + k (SM_PARAM_MIN_DISP) and dmax is negative at the columns x < d0, which have no candidate.
+// A previous pixel q with no existing k acts as a q outside the image: every L(q, .) is kInf, so M = kInf,
+// min(...) = kInf as well (kInf + P < 2^21, no wrap) and min(...) - M = 0, L(p, .) = C(p, .), without a branch.
 #include "bm_common.h"
 
 namespace sm {
@@ -69,7 +76,7 @@ __device__ __forceinline__ uint32_t path_best(const uint32_t (&Lp)[N], int j, ui
 // and 8 d per instruction, all of a tile's loads in flight together; other widths load u16 per lane.
 template <int NJ, bool VEC>
 __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
-                                                   uint32_t P2, uint32_t* __restrict__ S) {
+                                                   uint32_t P2, int ka, int kb, uint32_t* __restrict__ S) {
     constexpr int LS = NJ * kTX + 2;
     __shared__ __align__(16) uint16_t tile[64 * LS];
     const int lane = threadIdx.x;
@@ -103,7 +110,7 @@ __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ 
         __syncthreads();
         for (int i = 0; i < n; ++i) {
             const int xi = dir ? n - 1 - i : i;
-            const int dmax = min(D - 1, W - (x0 + xi));   // d <= dmax exist at this column
+            const int dmax = min(D - 1, ka + kb * (x0 + xi));   // d <= dmax exist at this column
             uint32_t m = Lp[0];
 #pragma unroll
             for (int j = 1; j < NJ; ++j) m = min(m, Lp[j]);
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ 
         }
         __syncthreads();
         if (lane < n) {
-            const int dmax = min(D - 1, W - (x0 + lane));
+            const int dmax = min(D - 1, ka + kb * (x0 + lane));
 #pragma unroll 8
             for (int d = 0; d <= dmax; ++d)
                 atomicAdd(&S[d * P + row + x0 + lane], (uint32_t)tile[(d / NJ) * LS + (d % NJ) * kTX + lane]);
@@ -146,7 +153,9 @@ __global__ __launch_bounds__(64) void sgm_h_kernel(const uint16_t* __restrict__ 
 // so the columns of all tiles cover every row exactly once, a lane's previous pixel on the path, q = p - rho, is the
 // one it held a row earlier, and its L stays in its registers.  A lane restarts also where x - dx is outside [0, W):
 // the column the path enters by, which is also where the wrap brings a lane back into the frame.  A lane at a
-// column >= W (the padding of the last tile) is idle: it loads and adds nothing and carries kInf.  The 32 columns of
+// column >= W (the padding of the last tile) is idle: it loads and adds nothing and carries kInf, and so is, with
+// either DIAG, a lane at a column where no d exists (SM_PAIRS_IN_VIEW, x < d0): both have a negative dmax.  The 32
+// columns of
 // a half wave stay one row segment, cut in two only at the wrap, so the cost loads and the atomic adds keep their
 // shape, shifted by s columns.  The d that exist change with the column: dmax is per lane and row, and the prefetch
 // queue follows the column kPF rows ahead.
@@ -154,7 +163,7 @@ constexpr int kPF = 4;
 constexpr int kVX = 32;   // columns per workgroup: each half of a wave is one d chunk of 32 columns
 template <int DPT, bool DIAG>
 __global__ __launch_bounds__(1024) void sgm_col_kernel(const uint16_t* __restrict__ C, int W, int H, int D, uint32_t P1,
-                                                       uint32_t P2, uint32_t* __restrict__ S) {
+                                                       uint32_t P2, int ka, int kb, uint32_t* __restrict__ S) {
     __shared__ uint32_t ex[2][3][32][kVX];
     const int lane = threadIdx.x & (kVX - 1), w = threadIdx.x / kVX, nw = blockDim.x / kVX;
     const int Wp = (int)gridDim.x * kVX;
@@ -165,7 +174,7 @@ __global__ __launch_bounds__(1024) void sgm_col_kernel(const uint16_t* __restric
     const int y0 = dy < 0 ? H - 1 : 0;
     // DIAG: one step along the row, modulo Wp
     auto slide = [&](int x) { x += dx; return x < 0 ? x + Wp : (x >= Wp ? x - Wp : x); };
-    auto dmax_at = [&](int x) { return x < W ? min(D - 1, W - x) : -1; };   // d <= dmax exist at this column
+    auto dmax_at = [&](int x) { return x < W ? min(D - 1, ka + kb * x) : -1; };   // d <= dmax exist at this column
     uint32_t Lp[DPT], Cq[kPF][DPT];
 #pragma unroll
     for (int j = 0; j < DPT; ++j) Lp[j] = kInf;
@@ -226,10 +235,15 @@ __global__ __launch_bounds__(1024) void sgm_col_kernel(const uint16_t* __restric
 // Left: the smallest existing d (d <= W - x) attaining min S, no threshold.  Right view: S_R(y, u, d) =
 // S(y, u + d, d) (StereoHelper.cpp:156-180) over the d whose pair (u + d, d) exists, u + 2 d <= W (which
 // implies u + d < W; d = 0 always exists); key = S << 8 | d, whose low byte is dR.
+// SM_PAIRS_IN_VIEW (in_view, d0; ka, kb as above): plane k is d = d0 + k, the left view walks k <= min(D - 1, x - d0)
+// and writes d0 + k, the right view is S_R(u, k) = S(u + d0 + k, k) over u + d0 + k <= W - 1, each of which exists
+// in the left view; its keys carry k, and d0 is added where they become the map (launch_keys_low_byte).  A pixel
+// with no candidate gets 0 in the left map and keeps the key ~0, which that step turns into 0.
 // T: uint32_t, the paths' sum S (< 2^19 with eight paths), or uint16_t, a box cost volume taken without SGM (SM_COST_CENSUS with
 // SM_AGG_BOX: the census cost, <= 62 * win^2 = 13950); either key fits 32 bits.
 template <typename T>
 __global__ __launch_bounds__(256) void sgm_wta_kernel(const T* __restrict__ S, int W, int H, int D,
+                                                      int ka, int kb, int in_view, int d0,
                                                       uint8_t* __restrict__ disp, int pitch,
                                                       uint32_t* __restrict__ rkeys) {
     const int nxb = (W + 255) / 256;
@@ -237,34 +251,36 @@ __global__ __launch_bounds__(256) void sgm_wta_kernel(const T* __restrict__ S, i
     if (x >= W) return;
     const int64_t P = (int64_t)W * H;
     const T* s = S + (int64_t)y * W + x;
-    const int dmax = min(D - 1, W - x);
+    const int dmax = min(D - 1, ka + kb * x);
     uint32_t best = 0xFFFFFFFFu;
     for (int d = 0; d <= dmax; ++d) best = min(best, ((uint32_t)s[d * P] << 8) | (uint32_t)d);
-    disp[(int64_t)y * pitch + x] = (uint8_t)(best & 0xFFu);
+    disp[(int64_t)y * pitch + x] = dmax < 0 ? (uint8_t)0 : (uint8_t)((best & 0xFFu) + (uint32_t)d0);
     if (rkeys) {
-        const int rmax = min(D - 1, (W - x) / 2);
+        const int rmax = min(D - 1, in_view ? W - 1 - x - d0 : (W - x) / 2);   // x + d0 + rmax <= W - 1
+        const T* sr = s + d0;
         uint32_t rb = 0xFFFFFFFFu;
-        for (int d = 0; d <= rmax; ++d) rb = min(rb, ((uint32_t)s[d * P + d] << 8) | (uint32_t)d);
+        for (int d = 0; d <= rmax; ++d) rb = min(rb, ((uint32_t)sr[d * P + d] << 8) | (uint32_t)d);
         rkeys[(int64_t)y * W + x] = rb;
     }
 }
 
 }  // namespace
 
-hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, uint32_t* S,
-                            hipStream_t s) {
+hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, int P2, int paths, const Pairs& pr,
+                            uint32_t* S, hipStream_t s) {
+    const int ka = pr.ka(W), kb = pr.kb();
     if (W <= 0 || H <= 0 || D < 1 || D > kMaxDisp || P1 < 0 || P2 < P1 || P2 > 65535) return hipErrorInvalidValue;
-    if (paths != 4 && paths != 8) return hipErrorInvalidValue;
+    if ((paths != 4 && paths != 8) || !pr.ok(D, 4095)) return hipErrorInvalidValue;
     const dim3 hgrid((unsigned)H, 2);
     const int nj = (D + 63) / 64;
 #define SM_SGM_H(n)                                                                                                  \
     do {                                                                                                            \
         if (W % 8 == 0 && reinterpret_cast<uintptr_t>(sad) % 16 == 0)                                               \
             hipLaunchKernelGGL((sgm_h_kernel<n, true>), hgrid, dim3(64), 0, s, sad, W, H, D, (uint32_t)P1,          \
-                               (uint32_t)P2, S);                                                                    \
+                               (uint32_t)P2, ka, kb, S);                                                            \
         else                                                                                                        \
             hipLaunchKernelGGL((sgm_h_kernel<n, false>), hgrid, dim3(64), 0, s, sad, W, H, D, (uint32_t)P1,         \
-                               (uint32_t)P2, S);                                                                    \
+                               (uint32_t)P2, ka, kb, S);                                                            \
     } while (0)
     if (nj == 1) SM_SGM_H(1);
     else if (nj == 2) SM_SGM_H(2);
@@ -279,7 +295,7 @@ hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, in
     const dim3 vblock((unsigned)((kVX * ((D + dpt - 1) / dpt) + 63) / 64 * 64));
 #define SM_SGM_COL(diag, grid)                                                                                       \
     hipLaunchKernelGGL((dpt == 2 ? sgm_col_kernel<2, diag> : (dpt == 4 ? sgm_col_kernel<4, diag> : sgm_col_kernel<8, diag>)), \
-                       grid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, S)
+                       grid, vblock, 0, s, sad, W, H, D, (uint32_t)P1, (uint32_t)P2, ka, kb, S)
     SM_SGM_COL(false, vgrid);
     e = hipGetLastError();
     if (e != hipSuccess || paths == 4) return e;
@@ -290,23 +306,25 @@ hipError_t launch_sgm_paths(const uint16_t* sad, int W, int H, int D, int P1, in
 
 namespace {
 template <typename T>
-hipError_t launch_wta(const T* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys, hipStream_t s) {
+hipError_t launch_wta(const T* S, int W, int H, int D, const Pairs& pr, uint8_t* disp, int out_pitch,
+                      uint32_t* right_keys, hipStream_t s) {
     const int64_t blocks = (int64_t)((W + 255) / 256) * H;
-    if (W <= 0 || H <= 0 || D < 1 || D > kMaxDisp || out_pitch < W || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sgm_wta_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, S, W, H, D, disp, out_pitch,
-                       right_keys);
+    if (W <= 0 || H <= 0 || D < 1 || D > kMaxDisp || out_pitch < W || blocks > 0x7FFFFFFF || !pr.ok(D, 255))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sgm_wta_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, S, W, H, D, pr.ka(W), pr.kb(),
+                       pr.in_view, pr.d0, disp, out_pitch, right_keys);
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, uint8_t* disp, int out_pitch, uint32_t* right_keys,
-                          hipStream_t s) {
-    return launch_wta(S, W, H, D, disp, out_pitch, right_keys, s);
+hipError_t launch_sgm_wta(const uint32_t* S, int W, int H, int D, const Pairs& pr, uint8_t* disp, int out_pitch,
+                          uint32_t* right_keys, hipStream_t s) {
+    return launch_wta(S, W, H, D, pr, disp, out_pitch, right_keys, s);
 }
 
-hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, uint8_t* disp, int out_pitch,
+hipError_t launch_cost_wta_u16(const uint16_t* C, int W, int H, int D, const Pairs& pr, uint8_t* disp, int out_pitch,
                                uint32_t* right_keys, hipStream_t s) {
-    return launch_wta(C, W, H, D, disp, out_pitch, right_keys, s);
+    return launch_wta(C, W, H, D, pr, disp, out_pitch, right_keys, s);
 }
 
 }  // namespace sm

@@ -10,6 +10,10 @@
 // come from 5 aligned dword LDS reads and 4 v_alignbyte_b32, |L - R| is formed 2 bytes per packed
 // 16-bit lane (v_pk_sub_i16 / v_pk_max_i16), and the 16 result bytes go out as one 16-B store (byte
 // stores when the plane layout is not 16-B aligned).
+//
+// d0 (SM_PARAM_MIN_DISP, the matching calls with SM_PAIRS_IN_VIEW alone; the public volume calls pass 0): plane k
+// holds the disparity d0 + k, dif[k][y][x] = |L(y,x) - R(y,x-d0-k)| for x >= d0 + k, 0 otherwise.  The kernel
+// forms de = d + d0 wherever it addresses the right row or masks, and keeps d for the plane.
 #include <algorithm>
 
 #include "bm_common.h"
@@ -59,7 +63,7 @@ __device__ __forceinline__ uint32_t absdiff_u8x4(uint32_t a, uint32_t b) {
 template <int KF>
 __global__ __launch_bounds__(kVT) void ad_volume_kernel(const uint8_t* __restrict__ L, const uint8_t* __restrict__ R,
                                                         int W, int H, int pitch, int64_t fstride, int D, int RB,
-                                                        int dsp, uint8_t* __restrict__ dif, int64_t dstride) {
+                                                        int dsp, uint8_t* __restrict__ dif, int64_t dstride, int d0) {
     constexpr int SEG = 16, NQ = 4;
     constexpr int kVPad = SEG;   // zero bytes in front of each staged R row (x - d down to -SEG)
     extern __shared__ __attribute__((aligned(16))) uint8_t rrow[];   // [RB][rstride]
@@ -124,10 +128,11 @@ __global__ __launch_bounds__(kVT) void ad_volume_kernel(const uint8_t* __restric
         for (int k = 0; k < KF; ++k) {
             if (fl[k] >= nflat) continue;
             const int i = fl[k] / nseg;
-            // R bytes at x0-d .. x0-d+15 from the padded row (index kVPad + x0 - d >= 0 while d <= x0 + 16;
-            // a larger d leaves every byte of the segment at x < d)
+            // R bytes at x0-de .. x0-de+15 from the padded row (index kVPad + x0 - de >= 0 while de <= x0 + 16;
+            // a larger de leaves every byte of the segment at x < de)
             uint32_t r[NQ];
-            const int start = kVPad + x0[k] - d;
+            const int de = d + d0;   // the disparity of plane d
+            const int start = kVPad + x0[k] - de;
             if (start >= 0) {
                 const int base = start & ~3, sh = start & 3;
                 const uint32_t* w = reinterpret_cast<const uint32_t*>(rrow + (size_t)i * rdw * 4 + base);
@@ -143,11 +148,11 @@ __global__ __launch_bounds__(kVT) void ad_volume_kernel(const uint8_t* __restric
             uint32_t o[NQ];
 #pragma unroll
             for (int q = 0; q < NQ; ++q) o[q] = absdiff_u8x4(l[k][q], r[q]);
-            if (x0[k] < d + SEG) {   // bytes with x < d are 0 (Device.cu:27-31 + the memset)
-                // dword q drops its low n = clamp(d - x0 - 4q, 0, 4) bytes: one 64-bit shift per dword
+            if (x0[k] < de + SEG) {   // bytes with x < de are 0 (Device.cu:27-31 + the memset)
+                // dword q drops its low n = clamp(de - x0 - 4q, 0, 4) bytes: one 64-bit shift per dword
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
-                    const int n = min(max(d - x0[k] - 4 * q, 0), 4);
+                    const int n = min(max(de - x0[k] - 4 * q, 0), 4);
                     o[q] &= (uint32_t)(~0ull << (8 * n));
                 }
             }
@@ -168,10 +173,10 @@ __global__ __launch_bounds__(kVT) void ad_volume_kernel(const uint8_t* __restric
 }  // namespace
 
 hipError_t launch_ad_volume(const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int64_t fstride, int batch,
-                            int D, uint8_t* dif, int64_t dstride, hipStream_t s) {
+                            int D, uint8_t* dif, int64_t dstride, hipStream_t s, int d0) {
     constexpr int SEG = 16;
     const int nseg = (W + SEG - 1) / SEG;
-    if (W <= 0 || H <= 0 || D <= 0 || batch <= 0 || nseg > 4 * kVT) return hipErrorInvalidValue;
+    if (W <= 0 || H <= 0 || D <= 0 || batch <= 0 || nseg > 4 * kVT || d0 < 0 || d0 > 4095) return hipErrorInvalidValue;
     // rows per block: up to SM_ADV_ROWS, at most 4 segments per thread
     int rb = SM_ADV_ROWS;
     while (rb > 1 && rb * nseg > 4 * kVT) --rb;
@@ -187,13 +192,13 @@ hipError_t launch_ad_volume(const uint8_t* L, const uint8_t* R, int W, int H, in
     const dim3 grid((unsigned)bands, (unsigned)batch, (unsigned)dsplit);
     if (kf <= 1)
         hipLaunchKernelGGL(ad_volume_kernel<1>, grid, dim3(kVT), lds, s, L, R, W, H, pitch, fstride, D, rb, dsplit, dif,
-                           dstride);
+                           dstride, d0);
     else if (kf == 2)
         hipLaunchKernelGGL(ad_volume_kernel<2>, grid, dim3(kVT), lds, s, L, R, W, H, pitch, fstride, D, rb, dsplit, dif,
-                           dstride);
+                           dstride, d0);
     else
         hipLaunchKernelGGL(ad_volume_kernel<4>, grid, dim3(kVT), lds, s, L, R, W, H, pitch, fstride, D, rb, dsplit, dif,
-                           dstride);
+                           dstride, d0);
     return hipGetLastError();
 }
 

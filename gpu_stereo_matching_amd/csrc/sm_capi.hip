@@ -174,8 +174,10 @@ using namespace smh;
 
 namespace {
 
-// What an entry point that honours SM_COST_CENSUS checks before it touches the device.
-int cost_check(const sm_handle* h, int width, int radius, unsigned flags) {
+// What an entry point that honours SM_COST_CENSUS and SM_PAIRS_IN_VIEW checks before it touches the device.
+int cost_check(const sm_handle* h, int width, int radius, int num_disp, unsigned flags) {
+    const int rc = pairs_check(h, flags, num_disp, false, nullptr);
+    if (rc) return rc;
     if (!(flags & SM_COST_CENSUS)) return SM_OK;
     if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, nullptr, nullptr);
     return census_check(width, radius, flags);
@@ -245,6 +247,11 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
     const int64_t P = (int64_t)W * H;
     const int64_t PB = P * batch;
     int sgm_p1 = 0, sgm_p2 = 0;
+    sm::Pairs pairs;   // SM_PAIRS_IN_VIEW and the handle's minimum disparity: the volume paths alone take them
+    {
+        const int rc = pairs_check(h, flags, D, false, &pairs);
+        if (rc) return rc;
+    }
     if (sgm) {   // before the other flags' checks: the combinations are its to reject
         const int rc = sgm_check(W, radius, flags, h->sgm_p1, h->sgm_p2, &sgm_p1, &sgm_p2);
         if (rc) return rc;
@@ -319,7 +326,7 @@ int run_device_body(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* 
     a.out_frame_stride = lstride;
     if (volume) {   // SGM and / or the census cost: the right view comes from the same volume as the left map
         const VolumeOut o{lmap, lpitch, lstride, lr ? right_map : nullptr};
-        int rc = run_volume(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, sgm, census, sgm_p1, sgm_p2, o);
+        int rc = run_volume(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, sgm, census, sgm_p1, sgm_p2, pairs, o);
         if (rc) return rc;
     } else if (guided) {
         sm::GuidedPass g{};   // d_lo 0, no keys
@@ -470,7 +477,7 @@ int host_match_rows(sm_handle* h, const uint8_t* left, const uint8_t* right, int
         rc = speckle_refuse(h, "a row band", "regions cross the bands (sm_group_block_match_batch_u8 runs whole frames)");
         if (rc) return rc;
     }
-    rc = cost_check(h, width, radius, flags);
+    rc = cost_check(h, width, radius, num_disp, flags);
     if (rc) return rc;
     rc = check_capacity(h, width, height, num_disp);
     if (rc) return rc;
@@ -683,6 +690,13 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         h->fill_gap = (int)value;
         return SM_OK;
     }
+    if (param == SM_PARAM_MIN_DISP) {
+        const int v = (int)value;
+        if (!(value >= 0.f) || value > 4095.f || (float)v != value)
+            return fail(SM_ERR_INVALID_ARG, "minimum disparity must be an integer in [0, 4095]");
+        h->min_disp = v;
+        return SM_OK;
+    }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);
 }
 
@@ -729,7 +743,7 @@ SM_API int sm_block_match_bgr_u8(sm_handle* h, const uint8_t* left_bgr, const ui
     if (!left_bgr || !right_bgr || !disp_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if ((channels != 3 && channels != 4) || pitch < width * channels || out_pitch < width)
         return fail(SM_ERR_INVALID_ARG, "bad BGR layout");
-    rc = cost_check(h, width, radius, flags);
+    rc = cost_check(h, width, radius, num_disp, flags);
     if (rc) return rc;
     rc = check_capacity(h, width, height, num_disp);
     if (rc) return rc;
@@ -791,7 +805,7 @@ SM_API int sm_match_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch < width");
     if (batch > 1 && (frame_stride < (int64_t)pitch * height || out_frame_stride < (int64_t)out_pitch * height))
         return fail(SM_ERR_INVALID_ARG, "frame strides overlap");
-    rc = cost_check(h, width, radius, flags);
+    rc = cost_check(h, width, radius, num_disp, flags);
     if (rc) return rc;
     SM_HIP(hipSetDevice(h->device));
     return run_device(h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp, flags, d_disp,

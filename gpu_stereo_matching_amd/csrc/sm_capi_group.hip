@@ -294,6 +294,8 @@ int group_bands(sm_group* g, const uint8_t* left, const uint8_t* right, int widt
         rc = speckle_refuse(w->h, "the row-band group call",
                             "regions cross the bands (sm_group_block_match_batch_u8 runs whole frames)");
         if (rc) return rc;
+        rc = pairs_refuse(w->h, flags, "the row-band group call");   // the whole-frame volume paths alone take them
+        if (rc) return rc;
     }
     if (flags & SM_AGG_SGM)   // the vertical paths run through every row of the frame
         return fail(SM_ERR_INVALID_ARG,
@@ -415,6 +417,10 @@ SM_API int sm_group_dslice_block_match_u8(sm_group* g, const uint8_t* left, cons
     int rc = group_frame_check(g, left, right, disp_out, width, height, pitch, out_pitch, flags);
     if (rc) return rc;
     const DsliceCfg cfg{width, height, radius, num_disp, (flags & SM_AGG_GUIDED) != 0, (flags & SM_LR_CHECK) != 0};
+    for (GroupWorker* w : g->w) {
+        rc = pairs_refuse(w->h, flags, "the d-slice group call");
+        if (rc) return rc;
+    }
     rc = dslice_check(cfg, flags);
     if (rc) return rc;
     for (GroupWorker* w : g->w) {

@@ -189,6 +189,8 @@ SM_API int sm_slice_keys_device(sm_handle* h, const uint8_t* d_left, const uint8
     if (rc) return rc;
     rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
     if (rc) return rc;
+    rc = pairs_refuse(h, 0u, "a slice-key call");
+    if (rc) return rc;
     rc = slice_check(d_lo, d_hi);
     if (rc) return rc;
     if (!d_left || !d_right || !d_keys) return fail(SM_ERR_INVALID_ARG, "null device pointer");
@@ -215,6 +217,8 @@ SM_API int sm_guided_slice_keys_device(sm_handle* h, const uint8_t* d_left, cons
     rc = speckle_refuse(h, "a slice-key call", "keys are no map; filter the combined map (sm_speckle_filter_device)");
     if (rc) return rc;
     rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
+    if (rc) return rc;
+    rc = pairs_refuse(h, 0u, "a slice-key call");
     if (rc) return rc;
     rc = guided_radius_check(radius);
     if (rc) return rc;
@@ -246,6 +250,8 @@ SM_API int sm_slice_keys_lr_device(sm_handle* h, const uint8_t* d_left, const ui
     rc = speckle_refuse(h, "a slice-key call", "keys are no map; filter the combined map (sm_speckle_filter_device)");
     if (rc) return rc;
     rc = fill_refuse(h, "a slice-key call", "keys are no map; fill the combined map (sm_fill_invalid_device)");
+    if (rc) return rc;
+    rc = pairs_refuse(h, flags, "a slice-key call");
     if (rc) return rc;
     if (flags & SM_AGG_SGM)
         return fail(SM_ERR_INVALID_ARG, "slice LR keys: SM_AGG_SGM's recursion over d crosses the slices");
@@ -304,6 +310,8 @@ SM_API int sm_dslice_rehearse_u8(sm_handle* h, const uint8_t* left, const uint8_
     rc = speckle_refuse(h, "the d-slice rehearsal", "the d-slice calls do not run it");
     if (rc) return rc;
     rc = fill_refuse(h, "the d-slice rehearsal", "the d-slice calls do not run it");
+    if (rc) return rc;
+    rc = pairs_refuse(h, flags, "the d-slice rehearsal");
     if (rc) return rc;
     const bool guided = (flags & SM_AGG_GUIDED) != 0;
     const DsliceCfg cfg{width, height, radius, num_disp, guided, (flags & SM_LR_CHECK) != 0};

@@ -49,14 +49,61 @@ int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out
     return SM_OK;
 }
 
+// ---- SM_PAIRS_IN_VIEW and SM_PARAM_MIN_DISP ----
+int pairs_check(const sm_handle* h, unsigned flags, int num_disp, bool subpix, sm::Pairs* out) {
+    sm::Pairs pr;
+    if (out) *out = pr;
+    if (!h) return fail(SM_ERR_INVALID_ARG, "null handle");
+    if (!(flags & SM_PAIRS_IN_VIEW)) {
+        if (h->min_disp > 0)
+            return fail(SM_ERR_INVALID_ARG,
+                        "SM_PARAM_MIN_DISP %d needs SM_PAIRS_IN_VIEW in the call's flags (0x%x): the reference's pair "
+                        "rule starts at d = 0", h->min_disp, flags);
+        return SM_OK;
+    }
+    if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_PAIRS_IN_VIEW does not combine with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID (flags "
+                    "0x%x): they are the reference-parity paths", flags);
+    if (!subpix && !(flags & (SM_AGG_SGM | SM_COST_CENSUS)))
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_PAIRS_IN_VIEW: the 8-bit AD SM_AGG_BOX call is the reference-parity path (its fused kernels "
+                    "and its threshold); the flag takes SM_AGG_SGM, SM_COST_CENSUS or a sub-pixel call (flags 0x%x)",
+                    flags);
+    pr.in_view = 1;
+    pr.d0 = h->min_disp;
+    const int limit = subpix ? 4095 : 255;
+    if (pr.d0 + num_disp - 1 > limit)
+        return fail(SM_ERR_INVALID_ARG,
+                    "SM_PARAM_MIN_DISP %d + num_disp %d - 1 = %d exceeds %d, the largest disparity of %s", pr.d0,
+                    num_disp, pr.d0 + num_disp - 1, limit, subpix ? "a 1/16-px map" : "an 8-bit map");
+    if (out) *out = pr;
+    return SM_OK;
+}
+
+int pairs_refuse(const sm_handle* h, unsigned flags, const char* call) {
+    if (flags & SM_PAIRS_IN_VIEW)
+        return fail(SM_ERR_INVALID_ARG, "%s cannot honour SM_PAIRS_IN_VIEW (flags 0x%x): it keeps no whole cost volume",
+                    call, flags);
+    if (h && h->min_disp > 0)
+        return fail(SM_ERR_INVALID_ARG,
+                    "%s cannot honour SM_PARAM_MIN_DISP %d: it runs the reference's pair rule, d from 0", call,
+                    h->min_disp);
+    return SM_OK;
+}
+
 // Every pass that keeps a cost volume, over `batch` frames, one frame after another through the volume workspace
 // (volume_layout):
 //   cost volume (AD, or the census words of both frames and their Hamming volume) -> box sums (u16)
 //   -> with SGM the zeroed S and the paths' sums over it (the handle's sgm_paths: four, or eight with the diagonals)
 //   -> one winner-takes-all over S (SGM) or the u16 costs: 8-bit maps with the right view's keys and their low
 //      byte, or subpix_wta_kernel (-> LR check; the two views' d0 of the check take the right-keys region).
+// pr (pairs_check): with SM_PAIRS_IN_VIEW plane k of every volume is d = pr.d0 + k, the cost launchers read the right
+// image pr.d0 columns further left, the paths and the WTA take the in-view prefix, and pr.d0 is added where the keys
+// become maps.  The shapes, the workspace and the launches are the same under either rule.
 int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-               int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const VolumeOut& o) {
+               int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const sm::Pairs& pr,
+               const VolumeOut& o) {
     const bool subpix = o.disp16 != nullptr;
     const int64_t P = (int64_t)W * H;
     const VolumeLayout w = volume_layout(P, D, sgm, census);
@@ -83,14 +130,14 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
         if (census) {
             SM_HIP(sm::launch_census(Lf, W, H, pitch, cl, s));
             SM_HIP(sm::launch_census(Rf, W, H, pitch, cr, s));
-            SM_HIP(sm::launch_census_volume(cl, cr, W, H, D, vol, s));
+            SM_HIP(sm::launch_census_volume(cl, cr, W, H, D, vol, s, pr.d0));
         } else {
-            SM_HIP(sm::launch_ad_volume(Lf, Rf, W, H, pitch, fstride, 1, D, vol, P * D, s));
+            SM_HIP(sm::launch_ad_volume(Lf, Rf, W, H, pitch, fstride, 1, D, vol, P * D, s, pr.d0));
         }
         SM_HIP(sm::launch_box_sad_volume(vol, W, H, radius, D, cost, s));
         if (sgm) {
             SM_HIP(hipMemsetAsync(S, 0, (size_t)(4 * P * D), s));
-            SM_HIP(sm::launch_sgm_paths(cost, W, H, D, p1, p2, h->sgm_paths, S, s));
+            SM_HIP(sm::launch_sgm_paths(cost, W, H, D, p1, p2, h->sgm_paths, pr, S, s));
         }
         if (subpix) {
             uint16_t* out = o.disp16 + f * o.ostride;
@@ -99,17 +146,17 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
             uint8_t* scratch = vol + w.rkeys;
             if (sgm)
                 SM_HIP(sm::launch_subpix_wta_u32(S, W, H, D, invalid_from, h->uniqueness, right_pairs, o.lr, out,
-                                                 o.opitch, rout, mout, scratch, s));
+                                                 o.opitch, rout, mout, scratch, s, pr));
             else
                 SM_HIP(sm::launch_subpix_wta_u16(cost, W, H, D, invalid_from, h->uniqueness, right_pairs, o.lr, out,
-                                                 o.opitch, rout, mout, scratch, s));
+                                                 o.opitch, rout, mout, scratch, s, pr));
             continue;
         }
         if (sgm)
-            SM_HIP(sm::launch_sgm_wta(S, W, H, D, o.lmap + f * o.lstride, o.lpitch, rkeys, s));
+            SM_HIP(sm::launch_sgm_wta(S, W, H, D, pr, o.lmap + f * o.lstride, o.lpitch, rkeys, s));
         else
-            SM_HIP(sm::launch_cost_wta_u16(cost, W, H, D, o.lmap + f * o.lstride, o.lpitch, rkeys, s));
-        if (o.right_map) SM_HIP(sm::launch_keys_low_byte(rkeys, P, o.right_map + f * P, s));
+            SM_HIP(sm::launch_cost_wta_u16(cost, W, H, D, pr, o.lmap + f * o.lstride, o.lpitch, rkeys, s));
+        if (o.right_map) SM_HIP(sm::launch_keys_low_byte(rkeys, P, o.right_map + f * P, s, pr.in_view, pr.d0));
     }
     return SM_OK;
 }
@@ -124,7 +171,7 @@ namespace {
 // The argument rules of the sub-pixel matching calls, before the device is touched; the resolved SGM penalties
 // come back through p1_out / p2_out.
 int subpix_check(const sm_handle* h, int width, int height, int pitch, int radius, int num_disp, unsigned flags,
-                 int* p1_out, int* p2_out) {
+                 int* p1_out, int* p2_out, sm::Pairs* pr) {
     // what the sub-pixel calls cannot do comes first and needs no handle; then the common argument checks
     if (flags & SM_MEDIAN)
         return fail(SM_ERR_INVALID_ARG,
@@ -138,7 +185,9 @@ int subpix_check(const sm_handle* h, int width, int height, int pitch, int radiu
         return fail(SM_ERR_INVALID_ARG, "sub-pixel: radius %d out of [0, %d] (the u16 cost volume)", radius,
                     sm::kMaxFastRadius);
     if (width > 4096) return fail(SM_ERR_INVALID_ARG, "sub-pixel: width %d out of [1, 4096]", width);
-    const int rc = check_geometry(h, width, height, pitch, radius, num_disp);
+    int rc = check_geometry(h, width, height, pitch, radius, num_disp);
+    if (rc) return rc;
+    rc = pairs_check(h, flags, num_disp, true, pr);
     if (rc) return rc;
     if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, p1_out, p2_out);
     if (flags & SM_COST_CENSUS) return census_check(width, radius, flags);
@@ -211,7 +260,8 @@ SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uin
                                   uint16_t* d_disp16, int out_pitch, int64_t out_frame_stride, uint16_t* d_right16,
                                   uint8_t* d_mask, void* stream) {
     int p1 = 0, p2 = 0;
-    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2);
+    sm::Pairs pr;
+    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2, &pr);
     if (rc) return rc;
     if (!d_left || !d_right || !d_disp16) return fail(SM_ERR_INVALID_ARG, "null device pointer");
     if (batch < 1) return fail(SM_ERR_INVALID_ARG, "batch %d < 1", batch);
@@ -221,7 +271,7 @@ SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uin
     SM_HIP(hipSetDevice(h->device));
     WsScope ws(h, stream_of(stream));
     rc = run_volume(ws, h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp,
-                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2,
+                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2, pr,
                     subpix_out(d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, flags));
     if (rc) return rc;
     return subpix_speckle(ws, h, d_disp16, width, height, out_pitch, batch, out_frame_stride, d_mask);
@@ -231,7 +281,8 @@ SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const ui
                                      int pitch, int radius, int num_disp, unsigned flags, uint16_t* disp16_out,
                                      uint16_t* right16_out, uint8_t* mask_out, int out_pitch) {
     int p1 = 0, p2 = 0;
-    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2);
+    sm::Pairs pr;
+    int rc = subpix_check(h, width, height, pitch, radius, num_disp, flags, &p1, &p2, &pr);
     if (rc) return rc;
     if (!left || !right || !disp16_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
@@ -249,7 +300,7 @@ SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const ui
     if (rc) return rc;
     WsScope ws(h, s);
     rc = run_volume(ws, h, h->d_left, h->d_right, width, height, width, 1, (int64_t)P, radius, num_disp,
-                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2,
+                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2, pr,
                     subpix_out(dq, width, (int64_t)P, right16_out ? dr : nullptr, mask_out ? dm : nullptr, flags));
     if (rc) return rc;
     rc = subpix_speckle(ws, h, dq, width, height, width, 1, (int64_t)P, mask_out ? dm : nullptr);
@@ -270,8 +321,14 @@ SM_API int sm_volume_wta_subpix_device(sm_handle* h, const void* d_vol, int elem
         return fail(SM_ERR_INVALID_ARG, "num_disp %d out of [1,%d]", num_disp, sm::kMaxDisp);
     if (elem_bytes != 2 && elem_bytes != 4)
         return fail(SM_ERR_INVALID_ARG, "elem_bytes %d: the volume holds uint16 (2) or uint32 (4) costs", elem_bytes);
-    if (flags & ~(unsigned)SM_LR_CHECK)
-        return fail(SM_ERR_INVALID_ARG, "sub-pixel WTA of a volume: flags are 0 or SM_LR_CHECK (0x%x)", flags);
+    if (flags & ~(unsigned)(SM_LR_CHECK | SM_PAIRS_IN_VIEW))
+        return fail(SM_ERR_INVALID_ARG,
+                    "sub-pixel WTA of a volume: flags are 0, SM_LR_CHECK, SM_PAIRS_IN_VIEW (0x%x)", flags);
+    sm::Pairs pr;   // with the flag, plane k of the caller's volume is d = SM_PARAM_MIN_DISP + k
+    {
+        const int rc = pairs_check(h, flags, num_disp, true, &pr);
+        if (rc) return rc;
+    }
     if (!d_vol || !d_disp16) return fail(SM_ERR_INVALID_ARG, "null device pointer");
     if (out_pitch < width) return fail(SM_ERR_INVALID_ARG, "out_pitch %d < width %d", out_pitch, width);
     SM_HIP(hipSetDevice(h->device));
@@ -279,16 +336,16 @@ SM_API int sm_volume_wta_subpix_device(sm_handle* h, const void* d_vol, int elem
     WsScope ws(h, s);
     const bool lr = (flags & SM_LR_CHECK) != 0;
     uint8_t* d0 = nullptr;
-    if (lr) {   // the two views' d0 go through the LR workspace
-        const int rc = ws.get(h->lr, 2 * (size_t)width * height, &d0);
+    if (lr) {   // the two views' d0 go through the LR workspace (16-bit each with SM_PAIRS_IN_VIEW)
+        const int rc = ws.get(h->lr, (pr.in_view ? 4 : 2) * (size_t)width * height, &d0);
         if (rc) return rc;
     }
     if (elem_bytes == 4)
         SM_HIP(sm::launch_subpix_wta_u32(static_cast<const uint32_t*>(d_vol), width, height, num_disp, invalid_from,
-                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, d0, s));
+                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, d0, s, pr));
     else
         SM_HIP(sm::launch_subpix_wta_u16(static_cast<const uint16_t*>(d_vol), width, height, num_disp, invalid_from,
-                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, d0, s));
+                                         h->uniqueness, 1, lr, d_disp16, out_pitch, d_right16, d_mask, d0, s, pr));
     return SM_OK;
 }
 

@@ -125,6 +125,7 @@ struct sm_handle {
     int speckle_size = 0;        // SM_PARAM_SPECKLE_SIZE: 0 off, else the largest region the matching calls remove
     int speckle_range = 1;       // SM_PARAM_SPECKLE_RANGE: whole disparities joined into one region, 0..255
     int fill_gap = 0;            // SM_PARAM_FILL_GAP: 0 off, else the longest run of a row the matching calls fill
+    int min_disp = 0;            // SM_PARAM_MIN_DISP: what plane 0 of a cost volume stands for (SM_PAIRS_IN_VIEW calls)
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -229,6 +230,14 @@ inline int fill_refuse(const sm_handle* h, const char* call, const char* why) {
 // against fill_pass_ok.
 int run_fill(hipStream_t s, void* map, int elem_bytes, int W, int H, int pitch, int batch, int64_t fstride, int max_gap);
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out);
+// SM_PAIRS_IN_VIEW and SM_PARAM_MIN_DISP (sm_capi_volume.hip), before any device work.
+// A call that keeps a cost volume: the flag needs one (SM_AGG_SGM, SM_COST_CENSUS, or `subpix`, a sub-pixel call,
+// with any aggregation it takes) and none of SM_AGG_GUIDED, SM_STAGED, SM_DEVICE_CU_GRID; a minimum disparity > 0
+// needs the flag; the largest disparity d0 + num_disp - 1 fits the map (255, sub-pixel 4095).  *out: the rule to run.
+int pairs_check(const sm_handle* h, unsigned flags, int num_disp, bool subpix, sm::Pairs* out);
+// A call that cannot honour either (`call`: the row-band, d-slice and slice-key calls): names the flag, or the
+// parameter when the handle's minimum disparity is > 0
+int pairs_refuse(const sm_handle* h, unsigned flags, const char* call);
 
 // SM_AGG_GUIDED's radii (bm_guided_plan.h): every guided entry rejects the others before it takes a workspace
 inline int guided_radius_check(int radius) {
@@ -283,7 +292,8 @@ struct VolumeOut {
 };
 // SM_AGG_SGM, SM_COST_CENSUS and the sub-pixel calls (sm_capi_volume.hip)
 int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
-               int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const VolumeOut& o);
+               int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const sm::Pairs& pr,
+               const VolumeOut& o);
 
 // ---- the box pass (sm_capi.hip) ----
 // Where the right view of a box pass goes, by what the plan was asked for.

@@ -30,12 +30,13 @@ class FrameStream:
     def __init__(self, matcher, batch: int, width: int, height: int, radius: int, num_disp: int,
                  agg: str = "box", lr_check: bool = False, device: Optional[int] = None,
                  consume: Optional[Callable[[np.ndarray], None]] = None, slots: int = 3, bgr: bool = False,
-                 rectify_maps=None, cost: str = "ad"):
+                 rectify_maps=None, cost: str = "ad", pairs: str = "reference"):
         """consume: optional callback given each completed batch as a view of its pinned buffer
         (no host copy; the view is only valid during the call).  Without it, submit()/flush()
         return copies.  bgr: inputs are [batch, H, W, 3] BGR frames, converted on the GPU.
         rectify_maps: (mapX1, mapY1, mapX2, mapY2) float32 [H, W] maps, applied on the GPU.
-        cost: 'ad' or 'census' (BlockMatcher.match_device's keyword; agg 'box' or 'sgm')."""
+        cost: 'ad' or 'census' (BlockMatcher.match_device's keyword; agg 'box' or 'sgm').
+        pairs: 'reference' or 'in-view' (the same call's keyword: SM_PAIRS_IN_VIEW, with agg 'sgm' or cost 'census')."""
         import torch
         self.consume = consume
         self.NS = slots
@@ -44,6 +45,7 @@ class FrameStream:
         self.B, self.W, self.H = batch, width, height
         self.r, self.D, self.agg, self.lr = radius, num_disp, agg, lr_check
         self.cost = cost
+        self.pairs = pairs
         dev = torch.device("cuda", matcher.device if device is None else device)
         self.dev = dev
         shape = (batch, height, width)
@@ -120,7 +122,7 @@ class FrameStream:
         self.s_comp.wait_event(self.ev_up[slot])
         ml, mr = self._front(dl, dr)
         self.m.match_device(ml, mr, self.r, self.D, out_t=self.d_out[slot], agg=self.agg, lr_check=self.lr,
-                            stream=self.s_comp, cost=self.cost)
+                            stream=self.s_comp, cost=self.cost, pairs=self.pairs)
         self.ev_done[slot].record(self.s_comp)
         with torch.cuda.stream(self.s_down):
             self.s_down.wait_event(self.ev_done[slot])

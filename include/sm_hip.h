@@ -88,7 +88,7 @@ enum {
                                SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID, and in the row-band group calls
                                (vertical paths cross the bands), the d-slice calls and the slice-key calls (the
                                recursion over d crosses the slices) */
-    SM_COST_CENSUS = 64u    /* census / Hamming matching cost (this build's extension) in place of the absolute
+    SM_COST_CENSUS = 64u,   /* census / Hamming matching cost (this build's extension) in place of the absolute
                                difference of gray values, with SM_AGG_BOX or SM_AGG_SGM; radius <= 7, width <= 4096.
                                Robust to exposure and gain differences between the cameras, and a bounded integer.
                                  census(y, x): uint64.  The window is 9 wide x 7 high, dx in [-4, 4], dy in [-3, 3],
@@ -112,6 +112,35 @@ enum {
                                device work, with SM_AGG_GUIDED, SM_STAGED or SM_DEVICE_CU_GRID, for radius > 7 or
                                width > 4096, in the row-band group calls (the replicated border would differ at
                                the band edges), and in the d-slice and slice-key calls */
+    SM_PAIRS_IN_VIEW = 128u /* the stereo-geometry pair rule (this build's extension; StereoSGBM's and libSGM's) for the
+                               calls that keep a cost volume, in place of the reference's x + d <= W.  With d0 =
+                               SM_PARAM_MIN_DISP, plane k of a volume stands for d = d0 + k, k = 0 .. num_disp - 1:
+                                 left view   (x, k) exists iff x - (d0 + k) >= 0: k <= min(num_disp - 1, x - d0), a
+                                             prefix, empty where x < d0;
+                                 right view  V_R(u, k) = V(u + d0 + k, k) over u + d0 + k <= width - 1; every such pair
+                                             exists in the left view.
+                               The volumes keep their shape and zero rule: plane k compares L(y, x) with
+                               R(y, x - d0 - k) and is 0 for x < d0 + k, and the box window sum is unchanged, so the
+                               window of a candidate with x - d < radius still contains zero taps (a bias towards
+                               large d in the leftmost columns; not normalised).  The recursion, the penalties, the
+                               16-bit bound, the first-minimum rule and the parabola (where 1 <= k0 < kmax) are
+                               SM_AGG_SGM's and the sub-pixel calls'; a previous pixel q with no existing k acts as a
+                               q outside the image, L(p, .) = C(p, .).  A pixel with no candidate gives 0 in the 8-bit
+                               and the 1/16-px map and 0 in the mask, in either view.  The maps hold the absolute
+                               disparity, d0 + k0 and 16 (d0 + k0) + delta, so the median, the LR check, the
+                               uniqueness test, speckle, fill and reproject run on them unchanged.  Near the right
+                               border the true disparity stays a candidate, and near the left border the d > x that
+                               the reference's zeroed volume lets win are gone.
+                               Honoured by sm_block_match_u8, _lr_u8, _bgr_u8, sm_match_device and
+                               sm_group_block_match_batch_u8 with SM_AGG_SGM or SM_COST_CENSUS; by
+                               sm_match_subpix_device and sm_block_match_subpix_u16 with every aggregation they take;
+                               by sm_volume_wta_subpix_device (the caller's plane k is d0 + k); accepted by
+                               sm_sgm_check.  sm_sgm_workspace_bytes and sm_census_workspace_bytes do not depend on
+                               it, and the public volume calls (sm_ad_volume_*, sm_census_volume_*,
+                               sm_sad_volume_device) keep d0 = 0.  SM_ERR_INVALID_ARG, naming the flag, before any
+                               device work: the 8-bit AD SM_AGG_BOX call without SM_COST_CENSUS (its fused kernels and
+                               its threshold are the reference-parity path), SM_AGG_GUIDED, SM_STAGED,
+                               SM_DEVICE_CU_GRID, and the row-band, d-slice and slice-key calls */
 };
 
 /* ---- scalar parameters (sm_set_param_f) ---- */
@@ -165,13 +194,20 @@ enum {
                                   ranges elsewhere; an integer n in 1 .. 2^20 that many at any launch size, also more
                                   than there are tiles.  The maps and keys do not depend on it.  Other values:
                                   SM_ERR_INVALID_ARG */
-    SM_PARAM_SGM_PATHS = 13    /* scan directions SM_AGG_SGM sums: 4 (default), rho = (+-1, 0), (0, +-1), or 8, those
+    SM_PARAM_SGM_PATHS = 13,   /* scan directions SM_AGG_SGM sums: 4 (default), rho = (+-1, 0), (0, +-1), or 8, those
                                   and the diagonals (+1, +1), (-1, +1), (+1, -1), (-1, -1), each under the same
                                   recursion, existence rule and penalties (a diagonal path starts, L = C, in the first
                                   row of its walk and in the column it enters the frame by).  S <= 8 * 65535 < 2^19;
                                   sm_sgm_check and sm_sgm_workspace_bytes do not depend on it, and everything after S
                                   (both views' WTA, median, LR check, the sub-pixel calls, speckle, fill) is
                                   unchanged.  Four more path passes per frame.  Other values: SM_ERR_INVALID_ARG */
+    SM_PARAM_MIN_DISP = 14     /* StereoSGBM's minDisparity for the SM_PAIRS_IN_VIEW calls: an integer 0 .. 4095,
+                                  default 0; other values: SM_ERR_INVALID_ARG.  The call searches d = d0 .. d0 +
+                                  num_disp - 1 in num_disp planes and its maps hold the absolute d.  The 8-bit calls
+                                  need d0 + num_disp - 1 <= 255, the 1/16-px calls <= 4095 (q <= 65528), else
+                                  SM_ERR_INVALID_ARG; d0 >= width is legal and gives the all-zero map.  With d0 > 0 every
+                                  matching call without SM_PAIRS_IN_VIEW is refused, naming the parameter (the
+                                  segment-tree calls aside, which have no disparity window of this kind) */
 };
 
 typedef struct sm_handle sm_handle;
@@ -375,7 +411,8 @@ SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t 
  * sm_volume_wta_subpix_device: the rule on a caller's d-major volume [num_disp][height][width] of uint16
  * (elem_bytes 2) or uint32 (elem_bytes 4) costs < 2^24, right view over u + 2 d <= W, with the handle's uniqueness;
  * invalid_from: 0 = no threshold, else the left view is invalid where b >= it; flags: 0 or SM_LR_CHECK (2 * P bytes
- * of the handle's LR workspace). */
+ * of the handle's LR workspace), each optionally with SM_PAIRS_IN_VIEW: plane k of the volume is then the disparity
+ * SM_PARAM_MIN_DISP + k under that flag's rules for both views (4 * P bytes of the LR workspace with SM_LR_CHECK). */
 SM_API int sm_match_subpix_device(sm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int width, int height,
                                   int pitch, int batch, int64_t frame_stride, int radius, int num_disp,
                                   unsigned flags, uint16_t *d_disp16, int out_pitch, int64_t out_frame_stride,

@@ -7,6 +7,9 @@ and that traffic over the time as a fraction of the 6.85 TB/s fill rate the proj
 --paths 8 times the same two calls with the diagonal paths on (SM_PARAM_SGM_PATHS 8) and writes
 profiles/sgm_bench_paths8.json; the default, 4, writes the files named here.
 
+--pairs in-view [--min-disp N] times the same two calls under SM_PAIRS_IN_VIEW, with SM_PARAM_MIN_DISP N, and writes
+profiles/sgm_bench_in_view.json; --disp stays the number of planes, so the search is N .. N + disp - 1.
+
 --cost census times the census cost (SM_COST_CENSUS) under --agg sgm or box instead, beside AD SGM from the same run
 of the same build, and writes profiles/census_bench.json (ms per map only: DESIGN §18).
 
@@ -144,6 +147,10 @@ def main(argv=None):
     ap.add_argument("--paths", type=int, default=4, choices=[4, 8],
                     help="scan directions of AD SGM (SM_PARAM_SGM_PATHS): 8 adds the diagonals and writes "
                          "profiles/sgm_bench_paths8.json")
+    ap.add_argument("--pairs", default="reference", choices=["reference", "in-view"],
+                    help="pair rule of AD SGM: in-view is SM_PAIRS_IN_VIEW and writes "
+                         "profiles/sgm_bench_in_view.json")
+    ap.add_argument("--min-disp", type=int, default=0, help="SM_PARAM_MIN_DISP, with --pairs in-view")
     ap.add_argument("--out", default=None,
                     help="default: profiles/sgm_bench.json, census_bench.json with --cost census, subpix_bench.json with --subpix")
     a = ap.parse_args(argv)
@@ -153,10 +160,16 @@ def main(argv=None):
         ap.error("--agg box is timed with --cost census only (the AD box path is bench.py's)")
     if a.paths == 8 and (a.subpix or a.cost != "ad"):
         ap.error("--paths 8 is timed on the AD SGM calls only")
+    if a.pairs != "in-view" and a.min_disp:
+        ap.error("--min-disp needs --pairs in-view")
+    if a.pairs == "in-view" and (a.subpix or a.cost != "ad"):
+        ap.error("--pairs in-view is timed on the AD SGM calls only")
     if a.out is None:
         name = "subpix_bench.json" if a.subpix else ("sgm_bench.json" if a.cost == "ad" else "census_bench.json")
         if a.paths == 8:
             name = "sgm_bench_paths8.json"
+        if a.pairs == "in-view":
+            name = "sgm_bench_in_view.json"
         a.out = os.path.join(ROOT, "profiles", name)
     import torch
     import gpu_stereo_matching_amd as sm
@@ -178,17 +191,23 @@ def main(argv=None):
     if a.paths == 8:
         res["workload"]["paths"] = 8
         res["algorithmic_bytes_formula"] = dict(FORMULA, paths_diagonal=FORMULA_DIAGONAL)
+    kw = {}
+    if a.pairs == "in-view":   # (a build without the flag is timed without the keyword)
+        res["workload"].update(pairs="in-view", min_disp=a.min_disp)
+        kw["pairs"] = "in-view"
     with sm.BlockMatcher(0, W, H, D) as m:
         if a.paths != 4:
             m.set_sgm_paths(a.paths)
+        if a.min_disp:
+            m.set_min_disp(a.min_disp)
         for name, lr in (("sgm", False), ("sgm_lr", True)):
             for _ in range(a.warmup):
-                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr)
+                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr, **kw)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(a.iters):
-                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr)
+                m.match_device(Lt, Rt, r, D, out_t=out_t, agg="sgm", lr_check=lr, **kw)
             e1.record()
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / a.iters
