@@ -681,6 +681,50 @@ class BlockMatcher:
         invalid when a disparity more than 1 away from its best costs less than best * 100 / (100 - u)."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_UNIQUENESS, float(u)))
 
+    def set_subpix_median(self, radius=0):
+        """The 16-bit median of the sub-pixel calls (SM_PARAM_SUBPIX_MEDIAN): with radius 1..3, match_subpix,
+        match_subpix_device and volume_wta_subpix_device filter both views' 1/16-px maps with the (2r+1)^2 median
+        before the LR check, which then runs on the filtered maps rounded to whole disparities; the right-view map
+        they return is the filtered one.  0 (the default) turns it off; other values are refused.  Every other call
+        ignores it."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_SUBPIX_MEDIAN, float(radius)))
+
+    def median16(self, map, radius: int) -> np.ndarray:  # noqa: A002
+        """The (2r+1)^2 median of a host uint16 map (sm_median_u16), replicate borders, radius 1..3, over the whole
+        16-bit value (0 is a value like any other).  Returns a new array."""
+        m = np.ascontiguousarray(map)
+        if m.dtype != np.uint16 or m.ndim != 2:
+            raise ValueError(f"map: expected a 2-D uint16 map, got {m.dtype} {m.shape}")
+        H, W = m.shape
+        out = np.empty((H, W), np.uint16)
+        _capi.check(self._lib.sm_median_u16(self._h, m.ctypes.data, W, H, W, int(radius), out.ctypes.data, W))
+        return out
+
+    def median16_device(self, src_t, radius: int, out_t=None, stream=None):
+        """Device form of :meth:`median16` (sm_median_u16_device), async on `stream`, not in place: src_t an int16
+        (uint16 bit patterns) cuda tensor [H, W] or [B, H, W] with contiguous rows (row and frame strides are passed
+        on, so a view cut out of a larger tensor works); out_t: an int16 tensor of the same shape with contiguous
+        rows, allocated when None.  Returns out_t."""
+        import torch
+        if src_t.dtype not in (torch.int16, torch.uint16) or src_t.dim() not in (2, 3) or not src_t.is_cuda \
+                or src_t.stride(-1) != 1:
+            raise ValueError("src_t must be an int16 [H, W] or [B, H, W] device tensor with contiguous rows")
+        if src_t.device.index != self.device:
+            raise ValueError(f"the map must be on cuda:{self.device}, the handle's device")
+        if out_t is None:
+            out_t = torch.empty(tuple(src_t.shape), dtype=src_t.dtype, device=src_t.device)
+        if out_t.dtype != src_t.dtype or out_t.shape != src_t.shape or out_t.stride(-1) != 1 \
+                or out_t.device != src_t.device:
+            raise ValueError("out_t must be a tensor of src_t's dtype and shape with contiguous rows")
+        B = 1 if src_t.dim() == 2 else src_t.shape[0]
+        H, W = src_t.shape[-2:]
+        fs = src_t.stride(0) if src_t.dim() == 3 else src_t.stride(-2) * H
+        ofs = out_t.stride(0) if out_t.dim() == 3 else out_t.stride(-2) * H
+        _capi.check(self._lib.sm_median_u16_device(
+            self._h, src_t.data_ptr(), W, H, src_t.stride(-2), B, fs, int(radius), out_t.data_ptr(),
+            out_t.stride(-2), ofs, self._stream_ptr(stream)))
+        return out_t
+
     def match_subpix(self, left, right, radius: int, num_disp: int, agg: str = "sgm", cost: str = "ad",
                      lr_check: bool = False, return_right: bool = False, return_mask: bool = False,
                      pairs: str = "reference"):

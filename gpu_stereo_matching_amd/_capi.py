@@ -42,6 +42,7 @@ SM_PARAM_FILL_GAP = 11
 SM_PARAM_BOX_QUEUE_WORKGROUPS = 12
 SM_PARAM_SGM_PATHS = 13
 SM_PARAM_MIN_DISP = 14
+SM_PARAM_SUBPIX_MEDIAN = 15
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (
@@ -64,6 +65,7 @@ EXPORTED = (
     "sm_reproject_u16",
     "sm_speckle_workspace_bytes", "sm_speckle_filter_device", "sm_speckle_filter_u8", "sm_speckle_filter_u16",
     "sm_fill_invalid_device", "sm_fill_invalid_u8", "sm_fill_invalid_u16",
+    "sm_median_u16_device", "sm_median_u16",
 )
 
 
@@ -165,6 +167,8 @@ def load(path: str = LIB_PATH):
     L.sm_fill_invalid_device.argtypes = [vp, vp, i, i, i, i, i, i64, i, vp]
     L.sm_fill_invalid_u8.argtypes = [vp, vp, i, i, i, i]
     L.sm_fill_invalid_u16.argtypes = [vp, vp, i, i, i, i]
+    L.sm_median_u16_device.argtypes = [vp, vp, i, i, i, i, i64, i, vp, i, i64, vp]
+    L.sm_median_u16.argtypes = [vp, vp, i, i, i, i, vp, i]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

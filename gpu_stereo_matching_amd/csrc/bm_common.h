@@ -253,6 +253,17 @@ hipError_t launch_census_volume(const uint64_t* cL, const uint64_t* cR, int W, i
 // (2r+1)^2 median with replicate borders, radius 1..3 (bm_post.hip)
 hipError_t launch_median(const uint8_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
                          uint8_t* dst, int dpitch, int64_t dstride, hipStream_t s);
+// The same for a 1/16-px map (bm_median16.hip): the element of rank 2r^2 + 2r of the window over the whole 16-bit
+// value, replicate borders, radius 1..3, not in place; pitches and strides in elements.  One launch for the batch.
+inline bool median16_pass_ok(int W, int H, int batch) {
+    return W >= 1 && H >= 1 && batch >= 1 && (int64_t)((W + 63) / 64) * ((H + 31) / 32) * batch <= 0x7FFFFFFFll;
+}
+hipError_t launch_median16(const uint16_t* src, int W, int H, int pitch, int64_t stride, int batch, int radius,
+                           uint16_t* dst, int dpitch, int64_t dstride, hipStream_t s);
+// The sub-pixel calls' LR check on two median-filtered maps: d = (q + 8) >> 4 of disp16 and of the dense right map
+// right_q (null: no check); occluded pixels get q = 0; mask (optional, dense) = final q != 0
+hipError_t launch_subpix_lr_q(const uint16_t* right_q, int W, int H, uint16_t* disp16, int pitch, uint8_t* mask,
+                              hipStream_t s);
 // speckle filter (bm_speckle.hip), in place on `batch` maps of T = uint8_t or uint16_t (pitch and fstride in
 // elements): every connected region (4-neighbours, both != 0, |a - b| <= max_diff) of at most max_size pixels is set
 // to 0, and `mask` (dense [batch][H][W], may be null) is cleared at the same pixels.  label / count: the planes of

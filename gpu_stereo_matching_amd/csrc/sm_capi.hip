@@ -697,6 +697,14 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         h->min_disp = v;
         return SM_OK;
     }
+    if (param == SM_PARAM_SUBPIX_MEDIAN) {
+        const int v = (int)value;
+        if (!(value >= 0.f) || value > 3.f || (float)v != value)
+            return fail(SM_ERR_INVALID_ARG,
+                        "SM_PARAM_SUBPIX_MEDIAN: the sub-pixel median's radius must be an integer in [0, 3] (0 = off)");
+        h->subpix_median = v;
+        return SM_OK;
+    }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);
 }
 

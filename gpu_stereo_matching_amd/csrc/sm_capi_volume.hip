@@ -97,7 +97,9 @@ int pairs_refuse(const sm_handle* h, unsigned flags, const char* call) {
 //   cost volume (AD, or the census words of both frames and their Hamming volume) -> box sums (u16)
 //   -> with SGM the zeroed S and the paths' sums over it (the handle's sgm_paths: four, or eight with the diagonals)
 //   -> one winner-takes-all over S (SGM) or the u16 costs: 8-bit maps with the right view's keys and their low
-//      byte, or subpix_wta_kernel (-> LR check; the two views' d0 of the check take the right-keys region).
+//      byte, or subpix_wta_kernel (-> LR check; the two views' d0 of the check take the right-keys region), or with
+//      SM_PARAM_SUBPIX_MEDIAN subpix_wta_kernel into planes of the `lr` workspace -> median16 of both views -> the
+//      check on the filtered maps (run_subpix_median).
 // pr (pairs_check): with SM_PAIRS_IN_VIEW plane k of every volume is d = pr.d0 + k, the cost launchers read the right
 // image pr.d0 columns further left, the paths and the WTA take the in-view prefix, and pr.d0 is added where the keys
 // become maps.  The shapes, the workspace and the launches are the same under either rule.
@@ -124,6 +126,16 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
     const uint32_t win = 2u * (uint32_t)radius + 1u;
     const uint32_t invalid_from = sgm || census ? 0u : 50u * win * win;   // Device.cu:37, the AD box path alone
     const int right_pairs = sgm || census ? 1 : 2;
+    // SM_PARAM_SUBPIX_MEDIAN: the views' unfiltered maps go through planes of the `lr` workspace, taken here, before
+    // the first launch, and reused frame after frame
+    const int med = subpix ? h->subpix_median : 0;
+    SubpixMedianWs mw;
+    if (med) {
+        uint8_t* planes = nullptr;
+        const int rc2 = ws.get(h->lr, subpix_median_bytes(P, o.lr, o.right16 != nullptr), &planes);
+        if (rc2) return rc2;
+        mw = subpix_median_ws(planes, P, o.lr, o.right16 != nullptr);
+    }
     for (int f = 0; f < batch; ++f) {
         const uint8_t* Lf = L + f * fstride;
         const uint8_t* Rf = R + f * fstride;
@@ -144,6 +156,17 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
             uint16_t* rout = o.right16 ? o.right16 + f * P : nullptr;
             uint8_t* mout = o.mask ? o.mask + f * P : nullptr;
             uint8_t* scratch = vol + w.rkeys;
+            if (med) {   // both views unchecked into the planes, then median -> check on the filtered maps -> mask
+                if (sgm)
+                    SM_HIP(sm::launch_subpix_wta_u32(S, W, H, D, invalid_from, h->uniqueness, right_pairs, false,
+                                                     mw.left, W, mw.right, nullptr, nullptr, s, pr));
+                else
+                    SM_HIP(sm::launch_subpix_wta_u16(cost, W, H, D, invalid_from, h->uniqueness, right_pairs, false,
+                                                     mw.left, W, mw.right, nullptr, nullptr, s, pr));
+                const int rc2 = run_subpix_median(s, mw, W, H, med, out, o.opitch, rout, o.lr, mout);
+                if (rc2) return rc2;
+                continue;
+            }
             if (sgm)
                 SM_HIP(sm::launch_subpix_wta_u32(S, W, H, D, invalid_from, h->uniqueness, right_pairs, o.lr, out,
                                                  o.opitch, rout, mout, scratch, s, pr));
@@ -175,8 +198,8 @@ int subpix_check(const sm_handle* h, int width, int height, int pitch, int radiu
     // what the sub-pixel calls cannot do comes first and needs no handle; then the common argument checks
     if (flags & SM_MEDIAN)
         return fail(SM_ERR_INVALID_ARG,
-                    "sub-pixel: SM_MEDIAN is not supported (the ctmf median is an 8-bit histogram; there is no 16-bit "
-                    "median)");
+                    "sub-pixel: SM_MEDIAN is not supported (the flag is the 8-bit ctmf median; the 1/16-px maps take "
+                    "the 16-bit median of SM_PARAM_SUBPIX_MEDIAN)");
     if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
         return fail(SM_ERR_INVALID_ARG,
                     "sub-pixel: SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID keep no cost volume to interpolate "
@@ -335,6 +358,22 @@ SM_API int sm_volume_wta_subpix_device(sm_handle* h, const void* d_vol, int elem
     hipStream_t s = stream_of(stream);
     WsScope ws(h, s);
     const bool lr = (flags & SM_LR_CHECK) != 0;
+    if (h->subpix_median) {   // SM_PARAM_SUBPIX_MEDIAN: WTA into planes of the LR workspace, median, check on the result
+        const int64_t P = (int64_t)width * height;
+        uint8_t* planes = nullptr;
+        int rc = ws.get(h->lr, subpix_median_bytes(P, lr, d_right16 != nullptr), &planes);
+        if (rc) return rc;
+        const SubpixMedianWs mw = subpix_median_ws(planes, P, lr, d_right16 != nullptr);
+        if (elem_bytes == 4)
+            SM_HIP(sm::launch_subpix_wta_u32(static_cast<const uint32_t*>(d_vol), width, height, num_disp,
+                                             invalid_from, h->uniqueness, 1, false, mw.left, width, mw.right, nullptr,
+                                             nullptr, s, pr));
+        else
+            SM_HIP(sm::launch_subpix_wta_u16(static_cast<const uint16_t*>(d_vol), width, height, num_disp,
+                                             invalid_from, h->uniqueness, 1, false, mw.left, width, mw.right, nullptr,
+                                             nullptr, s, pr));
+        return run_subpix_median(s, mw, width, height, h->subpix_median, d_disp16, out_pitch, d_right16, lr, d_mask);
+    }
     uint8_t* d0 = nullptr;
     if (lr) {   // the two views' d0 go through the LR workspace (16-bit each with SM_PAIRS_IN_VIEW)
         const int rc = ws.get(h->lr, (pr.in_view ? 4 : 2) * (size_t)width * height, &d0);

@@ -96,7 +96,9 @@ struct sm_handle {
     uint8_t* d_right = nullptr;
     uint8_t* d_disp = nullptr;
     // Workspaces of the passes, grown on demand and shared by calls on any stream (WsScope):
-    smh::SharedBuf lr;      // dense planes: raw left map (median), right map, filtered right map, mirrored pair
+    // dense planes: raw left map (median), right map, filtered right map, mirrored pair; the sub-pixel calls' d0
+    // planes (volume call) or their unfiltered views (SM_PARAM_SUBPIX_MEDIAN, SubpixMedianWs)
+    smh::SharedBuf lr;
     smh::SharedBuf rpart;   // fused right view: per-tile right-key partials
     // cost volumes, V planes of the wide path, right keys.  64 readable bytes past the end: box_sad_kernel reads
     // whole 8-byte words at the planes' last bytes
@@ -126,6 +128,7 @@ struct sm_handle {
     int speckle_range = 1;       // SM_PARAM_SPECKLE_RANGE: whole disparities joined into one region, 0..255
     int fill_gap = 0;            // SM_PARAM_FILL_GAP: 0 off, else the longest run of a row the matching calls fill
     int min_disp = 0;            // SM_PARAM_MIN_DISP: what plane 0 of a cost volume stands for (SM_PAIRS_IN_VIEW calls)
+    int subpix_median = 0;       // SM_PARAM_SUBPIX_MEDIAN: 0 off, 1..3 the sub-pixel calls' median radius (bm_median16.hip)
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -229,6 +232,28 @@ inline int fill_refuse(const sm_handle* h, const char* call, const char* why) {
 // workspace, so it joins no WsScope (sm_capi_fill.hip).  The arguments have been checked, except the frame
 // against fill_pass_ok.
 int run_fill(hipStream_t s, void* map, int elem_bytes, int W, int H, int pitch, int batch, int64_t fstride, int max_gap);
+// SM_PARAM_SUBPIX_MEDIAN (sm_capi_median16.hip): the sub-pixel calls' steps between the two views' WTA and the
+// speckle filter, one frame at a time through dense uint16 planes of P = W * H elements in the `lr` workspace:
+// [left q][right q][filtered right q], the second only with a right view (SM_LR_CHECK, or a right16 output) and the
+// third only when the check runs without a right16 output.  The caller takes subpix_median_bytes from the workspace
+// before its first launch and has the WTA write the unfiltered views into `left` and `right`.
+struct SubpixMedianWs {
+    uint16_t *left = nullptr, *right = nullptr, *right_out = nullptr;
+};
+inline size_t subpix_median_bytes(int64_t P, bool lr, bool right16) {
+    return (size_t)(2 * P) * (lr && !right16 ? 3 : lr || right16 ? 2 : 1);
+}
+inline SubpixMedianWs subpix_median_ws(uint8_t* base, int64_t P, bool lr, bool right16) {
+    SubpixMedianWs w;
+    w.left = reinterpret_cast<uint16_t*>(base);
+    if (lr || right16) w.right = w.left + P;
+    if (lr && !right16) w.right_out = w.left + 2 * P;
+    return w;
+}
+// median16 of w.left into disp16 and of w.right into right16 (or w.right_out); with lr the check on (q + 8) >> 4 of
+// the two filtered maps; mask (optional) = final q != 0
+int run_subpix_median(hipStream_t s, const SubpixMedianWs& w, int W, int H, int radius, uint16_t* disp16, int pitch,
+                      uint16_t* right16, bool lr, uint8_t* mask);
 int sgm_check(int width, int radius, unsigned flags, int p1, int p2, int* p1_out, int* p2_out);
 // SM_PAIRS_IN_VIEW and SM_PARAM_MIN_DISP (sm_capi_volume.hip), before any device work.
 // A call that keeps a cost volume: the flag needs one (SM_AGG_SGM, SM_COST_CENSUS, or `subpix`, a sub-pixel call,

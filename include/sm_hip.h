@@ -201,13 +201,18 @@ enum {
                                   sm_sgm_check and sm_sgm_workspace_bytes do not depend on it, and everything after S
                                   (both views' WTA, median, LR check, the sub-pixel calls, speckle, fill) is
                                   unchanged.  Four more path passes per frame.  Other values: SM_ERR_INVALID_ARG */
-    SM_PARAM_MIN_DISP = 14     /* StereoSGBM's minDisparity for the SM_PAIRS_IN_VIEW calls: an integer 0 .. 4095,
+    SM_PARAM_MIN_DISP = 14,    /* StereoSGBM's minDisparity for the SM_PAIRS_IN_VIEW calls: an integer 0 .. 4095,
                                   default 0; other values: SM_ERR_INVALID_ARG.  The call searches d = d0 .. d0 +
                                   num_disp - 1 in num_disp planes and its maps hold the absolute d.  The 8-bit calls
                                   need d0 + num_disp - 1 <= 255, the 1/16-px calls <= 4095 (q <= 65528), else
                                   SM_ERR_INVALID_ARG; d0 >= width is legal and gives the all-zero map.  With d0 > 0 every
                                   matching call without SM_PAIRS_IN_VIEW is refused, naming the parameter (the
                                   segment-tree calls aside, which have no disparity window of this kind) */
+    SM_PARAM_SUBPIX_MEDIAN = 15 /* radius of the 16-bit median the sub-pixel calls run on both views' 1/16-px maps
+                                  before the LR check: an integer 0..3, 0 (default) = off; other values:
+                                  SM_ERR_INVALID_ARG, and the parameter keeps its value.  Read by sm_match_subpix_device,
+                                  sm_block_match_subpix_u16 and sm_volume_wta_subpix_device alone (see "sub-pixel
+                                  disparities" and "16-bit median" below); every other call ignores it */
 };
 
 typedef struct sm_handle sm_handle;
@@ -401,8 +406,9 @@ SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t 
  * The arithmetic is exact for V < 2^24 (the bound under which the 8-bit (V << 8 | d) key fits 32 bits).
  *
  * sm_match_subpix_device: flags SM_AGG_BOX or SM_AGG_SGM, optionally | SM_COST_CENSUS | SM_LR_CHECK; radius <= 7,
- * width <= 4096.  SM_MEDIAN (the ctmf median is an 8-bit histogram), SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID
- * (no cost volume to interpolate) return SM_ERR_INVALID_ARG before any device work.  d_disp16: [batch][height]
+ * width <= 4096.  SM_MEDIAN (the flag is the 8-bit ctmf median; these calls take SM_PARAM_SUBPIX_MEDIAN, below),
+ * SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID (no cost volume to interpolate) return SM_ERR_INVALID_ARG before any
+ * device work.  d_disp16: [batch][height]
  * [out_pitch], out_pitch and out_frame_stride in uint16 elements; d_right16 / d_mask: dense [batch][height][width],
  * either may be NULL.  Frames of a batch run one after another through the handle's volume workspace:
  * sm_sgm_workspace_bytes / sm_census_workspace_bytes as for the 8-bit call, 3 * P * num_disp + 4 * P (each part
@@ -412,7 +418,21 @@ SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t 
  * (elem_bytes 2) or uint32 (elem_bytes 4) costs < 2^24, right view over u + 2 d <= W, with the handle's uniqueness;
  * invalid_from: 0 = no threshold, else the left view is invalid where b >= it; flags: 0 or SM_LR_CHECK (2 * P bytes
  * of the handle's LR workspace), each optionally with SM_PAIRS_IN_VIEW: plane k of the volume is then the disparity
- * SM_PARAM_MIN_DISP + k under that flag's rules for both views (4 * P bytes of the LR workspace with SM_LR_CHECK). */
+ * SM_PARAM_MIN_DISP + k under that flag's rules for both views (4 * P bytes of the LR workspace with SM_LR_CHECK).
+ *
+ * SM_PARAM_SUBPIX_MEDIAN = r in 1..3 (all three calls): per frame, both views' WTA, parabola, uniqueness and threshold
+ * run as above, without the check, into temporary uint16 planes; the (2r+1)^2 16-bit median (sm_median_u16_device's
+ * rule; an invalid pixel's 0 is a value like any other) of the left plane goes to the caller's map and that of the
+ * right plane to right16, which therefore returns the filtered right map; the right view is computed and filtered
+ * only with SM_LR_CHECK or a right16 output.  With SM_LR_CHECK the rule above then runs on d = (q' + 8) >> 4 of the
+ * two filtered maps, the 1/16-px values rounded to whole disparities (32-bit arithmetic: d reaches 4096 under
+ * SM_PAIRS_IN_VIEW): occluded when x - d < 0, d == 0 or |d - d_R(x - d)| > 1, and occluded pixels get q = 0.  The mask
+ * is (final q != 0), with or without the check.  Then the speckle filter and the row fill, as without the median.
+ * This is the order of the 8-bit calls under SM_MEDIAN | SM_LR_CHECK: median of both maps, then the check.
+ * The temporary planes, 2 * P bytes each, are one (no right view), two, or three (SM_LR_CHECK without right16) planes
+ * of the handle's LR workspace, taken before the first launch and reused by every frame of a batch: at most 6 * P
+ * bytes on top of sm_sgm_workspace_bytes / sm_census_workspace_bytes, whose values do not change; the check's
+ * d0 planes are not used.  With the parameter at 0 the calls launch and allocate exactly what they did without it. */
 SM_API int sm_match_subpix_device(sm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int width, int height,
                                   int pitch, int batch, int64_t frame_stride, int radius, int num_disp,
                                   unsigned flags, uint16_t *d_disp16, int out_pitch, int64_t out_frame_stride,
@@ -431,6 +451,23 @@ SM_API int sm_reproject_device(sm_handle *h, const uint16_t *d_disp16, int width
                                const double *Q, float *d_xyz, int xyz_pitch, void *stream);
 SM_API int sm_reproject_u16(sm_handle *h, const uint16_t *disp16, int width, int height, int pitch, const double *Q,
                             float *xyz_out, int xyz_pitch);
+
+/* ---- 16-bit median: the (2r+1)^2 median of a 1/16-px map (this build's extension) ----
+ * dst(y, x) = the element of rank 2 r^2 + 2 r (0-based) of the (2r+1)^2 window of src around (y, x), coordinates
+ * clamped to the frame (replicate borders), over the whole 16-bit value: 0x00FF < 0x0100, and 0 is a value like any
+ * other, so a pixel with enough invalid neighbours becomes invalid and an isolated hole is closed.  All integer.  Not
+ * in place: d_dst must differ from d_src.  Columns >= width and rows >= height of dst are never written, and those of
+ * src never read.  On uint8 values held in uint16 it equals sm_median_u8_device.
+ * sm_median_u16_device: `batch` device maps, pitch / dst_pitch and frame_stride / dst_frame_stride in uint16
+ * elements; asynchronous on `stream`; one launch, no workspace.  Every argument is checked before the device is
+ * touched, each refusal naming what was wrong: radius in 1..3, the frame size, batch >= 1, both pitches >= width, the
+ * pointers (null, or d_src == d_dst), frame strides that overlap (batch > 1), the handle and its capacity.
+ * sm_median_u16: the same on one host frame, synchronous, staged through the handle. */
+SM_API int sm_median_u16_device(sm_handle *h, const uint16_t *d_src, int width, int height, int pitch, int batch,
+                                int64_t frame_stride, int radius, uint16_t *d_dst, int dst_pitch,
+                                int64_t dst_frame_stride, void *stream);
+SM_API int sm_median_u16(sm_handle *h, const uint16_t *src, int width, int height, int pitch, int radius,
+                         uint16_t *dst, int dst_pitch);
 
 /* ---- speckle filter: StereoSGBM's speckleWindowSize / speckleRange (this build's extension) ----
  * OpenCV's filterSpeckles(img, newVal = 0, maxSpeckleSize, maxDiff) on a uint8 map or a uint16 (1/16 px) map, in
