@@ -1,5 +1,5 @@
 // bm_box_mfma.hip — the plain box matcher (bm_box.hip's semantics, bit-exact) with both window sums on the
-// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22, §24, §30).
+// matrix pipe of gfx950: v_mfma_f32_16x16x32_f16 against banded 0/1 matrices (DESIGN §19, §21, §22, §24, §30, §34).
 //
 // Scope: left view only (no fused right view), radius 1..kMaxFastRadius, valid_mode 0, d_max 64..256.
 //
@@ -36,7 +36,11 @@
 // 16-column block) packed to f16 is half of a stage-2 B operand; two adjacent column blocks make its K = 32 in
 // the order (4g + j, 16 + 4g + j), and the constant horizontal band (the A operand) is built in that order.
 // R sits in LDS column-major ([column][64 rows] f16, 128 B per column, 16-B row groups XOR-swizzled by the
-// column), so a lane's R operand for any d is one ds_read_b128 at column x - d.
+// column), so a lane's R operand for any d is one ds_read_b128 at column x - d.  The rows of a column are permuted
+// (staged_row): row group 4c + g holds the rows 32c + 4g + j and 32c + 16 + 4g + j, j = 0..3, so that a lane's eight
+// AD registers hold, from register 2 ob on, the 32 input rows from the first row of output row block ob on, in that
+// same K order.  The paired loop sums each row block with one MFMA on its four registers against one band (DESIGN
+// §34); the one-d-per-pass loop multiplies the two chunks as read, the middle block from both.
 #include <atomic>
 #include <type_traits>
 
@@ -49,6 +53,7 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u8 __attribute__((ext_vector_type(8)));
 
 constexpr int kT = 64;          // input tile edge
 constexpr int kNW = 4;          // waves per workgroup, one per SIMD
@@ -91,8 +96,16 @@ struct MG {
     static_assert((int64_t)(2 * R + 1) * (2 * R + 1) * 255 * 256 + 255 < (1 << 24), "keys exact in f32");
 };
 
-// byte offset of 16-B row group q (rows 8q..8q+7) of staged column `col`
+// byte offset of 16-B row group q of staged column `col`
 __device__ __forceinline__ int slot(int col, int q) { return col * kColB + ((q ^ ((col >> 1) & 7)) << 4); }
+
+// The staged row that element i of row group q holds.  Group q = 4c + g is what lane group g reads of the 32-row
+// chunk c: rows 32c + 4g + i (i < 4) and 32c + 16 + 4g + (i - 4) (i >= 4), the K order of a stage-2 operand.  A
+// lane's two chunks are then eight registers in which the dwords 2 ob .. 2 ob + 3 hold the rows 16 ob + ko(g, j),
+// ko = j < 4 ? 4g + j : 16 + 4g + (j - 4): the 32 input rows from output row block ob's first on
+__device__ __forceinline__ constexpr int staged_row(int q, int i) {
+    return 32 * (q >> 2) + 4 * (q & 3) + (i < 4 ? i : 12 + i);
+}
 
 // eight rows of one element (4 columns x 8 rows) as f16 1024 + v into columns `col`.. of row group q
 __device__ __forceinline__ void stage_pack(const uint32_t (&w)[8], uint8_t* dst, int col, int q) {
@@ -114,7 +127,7 @@ __device__ __forceinline__ void stage_cols(const uint8_t* img, int ytop, int xle
         const int q = e / NC4, j = e - q * NC4;
         uint32_t w[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = ld_image_u32(img, ytop + 8 * q + i, xleft + 4 * j, W, H, pitch);
+        for (int i = 0; i < 8; ++i) w[i] = ld_image_u32(img, ytop + staged_row(q, i), xleft + 4 * j, W, H, pitch);
         stage_pack(w, dst, 4 * j, q);
     }
 }
@@ -168,6 +181,17 @@ __device__ __forceinline__ uint2 pack_f16(f4 v) {
 
 __device__ __forceinline__ f4 mfma(u4 a, u4 b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
+}
+
+// The 32 input rows of output row block ob as a stage-1 A operand: dwords 2 ob .. 2 ob + 3 of a lane's eight AD
+// registers (staged_row).  The vector passes through an empty asm first (no instruction is emitted): the three
+// operands are then overlapping views of one 8-register tuple; left to itself the compiler splits the vector into
+// three tuples and copies four registers per view
+__device__ __forceinline__ u4 ad_view(u8& ad, int ob) {
+    asm volatile("" : "+v"(ad));
+    return ob == 0   ? __builtin_shufflevector(ad, ad, 0, 1, 2, 3)
+           : ob == 1 ? __builtin_shufflevector(ad, ad, 2, 3, 4, 5)
+                     : __builtin_shufflevector(ad, ad, 4, 5, 6, 7);
 }
 
 // WALK: the workgroup walks a range of tiles; false: one tile per workgroup, the tile loop and everything carried
@@ -226,30 +250,33 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
     const int d_lo = a.d_lo, d_hi = a.d_hi;
 
     // ---- constant bands ----
-    // vertical (B operand of stage 1): element j is input row k = 8g + j of a 32-row chunk against output row
-    // n = l16 of a 16-row block; the chunk starts `off` rows past the block: 1.0 where 0 <= off + k - n <= 2R
-    u4 bv0, bvm, bvp;   // off = 0, -16, +16
+    // vertical (B operand of stage 1): a 32-row view of a lane's AD registers starts at its output row block's first
+    // row (staged_row), so K slot (g, j) is input row ko = j < 4 ? 4g + j : 16 + 4g + (j - 4) of the block against
+    // output row n = l16: 1.0 where 0 <= ko - n <= 2R, one band for every row block.  The one-d-per-pass loop (run())
+    // multiplies the two chunks as they are read, rows 32c + ko, and needs two more: bv4, a chunk against the row
+    // block 16 rows down (the middle block in chunk 0, the fourth in chunk 1): 1.0 where 0 <= ko - 16 - n <= 2R, and
+    // bvp, chunk 1 against the middle block, 16 rows up: 1.0 where 0 <= ko + 16 - n <= 2R
+    u4 bv, bv4, bvp;
     // horizontal (A operand of stage 2): 256.0 where 0 <= xin - l16 <= 2R; K = two 16-column blocks, elements
     // 0..3 of a lane the columns 4g.. of one and 4..7 of the other: bh with the left block first, bhs swapped
     u4 bh, bhs;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        uint32_t w0 = 0, wm = 0, wp = 0, wh = 0, ws = 0;
+        uint32_t wv = 0, w4 = 0, wp = 0, wh = 0, ws = 0;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int j = 2 * m + e;
-            const int dv = 8 * g + j - l16;
-            const int xin = j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4);
+            const int xin = j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4);   // ko as well
             const int dh = xin - l16;
             const int ds = (j < 4 ? 16 + 4 * g + j : 4 * g + (j - 4)) - l16;
-            w0 |= (dv >= 0 && dv <= 2 * R ? 0x3C00u : 0u) << (16 * e);
-            wm |= (dv - 16 >= 0 && dv - 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
-            wp |= (dv + 16 >= 0 && dv + 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            wv |= (dh >= 0 && dh <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            w4 |= (dh - 16 >= 0 && dh - 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
+            wp |= (dh + 16 >= 0 && dh + 16 <= 2 * R ? 0x3C00u : 0u) << (16 * e);
             wh |= (dh >= 0 && dh <= 2 * R ? 0x5C00u : 0u) << (16 * e);
             ws |= (ds >= 0 && ds <= 2 * R ? 0x5C00u : 0u) << (16 * e);
         }
-        bv0[m] = w0;
-        bvm[m] = wm;
+        bv[m] = wv;
+        bv4[m] = w4;
         bvp[m] = wp;
         bh[m] = wh;
         bhs[m] = ws;
@@ -310,10 +337,11 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         auto issue_prefetch = [&] {
             if (prefetch) {
                 const CarriedElem<G::NEW0, G::NEW4> ce(per_tile(tid));
-                const uint8_t* p = (ce.right ? Rf : Lf) + (int64_t)(y0 - R + 8 * ce.q) * a.pitch +
+                const uint8_t* p = (ce.right ? Rf : Lf) + (int64_t)(y0 - R + staged_row(ce.q, 0)) * a.pitch +
                                    ((ce.right ? nxr : nxl) + ce.dx);
+                // (rows relative to the group's first: staged_row(q, i) - staged_row(q, 0) does not depend on q)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)i * a.pitch, 4);
+                for (int i = 0; i < 8; ++i) __builtin_memcpy(&pw[i], p + (int64_t)staged_row(0, i) * a.pitch, 4);
             }
         };
         // NP = 1: before the disparity loops, which cover the latency.  NP = 2: after both loops, whose order needs
@@ -377,13 +405,15 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                             }
                             const u4 ad0 = abs_diff(l0, r0, keep);
                             const u4 ad1 = abs_diff(l1, r1, keep);
-                            // output row blocks 0..NOB-1 of this column block from the two 32-row chunks
+                            // output row blocks 0..NOB-1 of this column block from the two 32-row chunks as they are
+                            // read: the middle block from both, 16 rows down in the first and 16 up in the second.  The
+                            // three views of run_paired cost this loop, which the compiler orders, its order
                             f4 sv[4];
-                            sv[0] = mfma(ad0, bv0, c1);
-                            sv[1] = mfma(ad0, bvm, c1);
+                            sv[0] = mfma(ad0, bv, c1);
+                            sv[1] = mfma(ad0, bv4, c1);
                             sv[1] = mfma(ad1, bvp, sv[1]);
-                            sv[2] = mfma(ad1, bv0, c1);
-                            if constexpr (NOB == 4) sv[3] = mfma(ad1, bvm, c1);
+                            sv[2] = mfma(ad1, bv, c1);
+                            if constexpr (NOB == 4) sv[3] = mfma(ad1, bv4, c1);
 #pragma unroll
                             for (int ob = 0; ob < NOB; ++ob) {
                                 const uint2 pk = pack_f16(sv[ob]);
@@ -437,14 +467,16 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         // MFMA vector work of its own wave that does not wait for it.  A column block is a sequence of
         // slots, one MFMA and two to four vector instructions each, a scheduling barrier after every slot, so the source
         // order is the machine order:
-        //   stage 1   the AD quads (4 v_pk_add_f16 + 4 v_and_b32) in the order (p0, chunk 0), (p1, chunk 0),
-        //             (p0, chunk 1), (p1, chunk 1): the row block that needs chunk 0 alone is summed first for both
-        //             disparities, so its converts, stage 2 and mins run under the rest.  A quad's two MFMAs issue
-        //             under the next quad, half a quad or more after its last AND; a convert follows the sum it reads
-        //             by three MFMAs
-        //   stage 2   of the output block to the left: its six MFMAs under the last converts and the mins of the rows
-        //             done; the mins of the middle row block wait for the first AD quad of the next column block
-        //   reads     chunk 0 of the next block goes out before the last three stage-2 MFMAs, chunk 1 with the
+        //   stage 1   a disparity's eight AD registers are one tuple, filled chunk 0 (4 v_pk_add_f16 + 4 v_and_b32), then
+        //             chunk 1 by halves, p0 and p1 alternating; row block ob is one MFMA on registers 2 ob .. 2 ob + 3
+        //             (ad_view): the first once chunk 0 is there, the middle one after the first half of
+        //             chunk 1, the last after the second.  An MFMA issues half a quad or more after the last AND it
+        //             reads; a convert follows the sum it reads by four MFMAs
+        //   stage 2   of the output block to the left: its six MFMAs in row block order under the last converts and
+        //             the mins of the rows done; the mins of the last row block wait for the first AD quad of the next
+        //             column block
+        //   reads     chunk 0 of the next block goes out before the last two stage-2 MFMAs (one slot earlier the
+        //             R = 1, d_max = 64 queue kernel spills a register), chunk 1 with the
         //             block's first quad (the R read its last quad needs one slot later), so only the first block of
         //             a pass begins with a wait (sending that block's reads out from the pass before was measured and
         //             bought nothing).  Reading all six ahead, or holding the next tile's staging loads
@@ -508,6 +540,9 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             int laddr_c[2] = {lds0 + laddr, (lds0 + laddr) ^ 64};
             // stage 1's C operand, held: left to the compiler it is rebuilt from scalar registers in every pass
             f4 c1p = c1;
+            // the eight AD registers of each disparity, one tuple for the whole loop: every pass writes all of them
+            // before it reads them
+            u8 ad8[2] = {};
             // The masks' scalars: wd = W - d, c0s = x0 - R - d, the image column of lane 0's staged column less d.  They
             // pass through an empty asm in every pass, so that nothing per-lane is derived from them ahead of the loop
             // and held over it
@@ -561,23 +596,24 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                 fetch(0, 0);
                 mk_keep(0, 0);
                 mk_keep(0, 1);
-                u4 om[2];   // stage 2 of the middle row block, carried to the next column block's first quad
+                u4 om[2];   // stage 2 of the last row block, carried to the next column block's first quad
 #pragma unroll
                 for (int cb = 0; cb <= NXB; ++cb) {
                     const bool s1 = cb < 4, s2 = cb >= 1;
                     const int xb = cb - 1;
-                    u4 ad[2][2];   // [p][chunk]
                     f4 sv[2][NOB];
                     u4 o[2][NOB];
-                    // elements 2h, 2h + 1 of AD quad (p, chunk c)
+                    // elements 2h, 2h + 1 of AD quad (p, chunk c): registers 4c + 2h, 4c + 2h + 1 of ad8[p]
                     auto half = [&](int p, int c, int h) {
 #pragma unroll
                         for (int m = 2 * h; m < 2 * h + 2; ++m) {
                             const uint32_t lm = lq[c][m], rm = rq[p][c][m];
                             const h2 df = __builtin_bit_cast(h2, lm) - __builtin_bit_cast(h2, rm);
-                            ad[p][c][m] = __builtin_bit_cast(uint32_t, df) & keep[p];
+                            ad8[p][4 * c + m] = __builtin_bit_cast(uint32_t, df) & keep[p];
                         }
                     };
+                    // row block ob of disparity p: its view of the eight AD registers against the one band
+                    auto stage1 = [&](int p, int ob) { sv[p][ob] = mfma(ad_view(ad8[p], ob), bv, c1p); };
                     auto cvt = [&](int p, int ob) {
                         const uint2 pk = pack_f16(sv[p][ob]);
                         t[p][ob][2 * (cb & 1)] = pk.x;
@@ -591,62 +627,58 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         fetch_r(cb, 0, 1);
                         half(0, 0, 0);
                         half(0, 0, 1);
-                        if (cb >= 2) mins(1, xb - 1, om[0], om[1]);
+                        if (cb >= 2) mins(2, xb - 1, om[0], om[1]);
                         slot_end();
                         fetch_r(cb, 1, 1);
-                        sv[0][0] = mfma(ad[0][0], bv0, c1p);
+                        stage1(0, 0);
                         half(1, 0, 0);
-                        slot_end();
-                        sv[0][1] = mfma(ad[0][0], bvm, c1p);
                         half(1, 0, 1);
                         slot_end();
                         half(0, 1, 0);
                         if (cb == NXB) step_addr();   // NXB = 3: the pass's last R read is out
                         slot_end();
-                        sv[1][0] = mfma(ad[1][0], bv0, c1p);
-                        half(0, 1, 1);
-                        slot_end();
-                        sv[1][1] = mfma(ad[1][0], bvm, c1p);
+                        stage1(1, 0);
                         half(1, 1, 0);
                         slot_end();
-                        sv[0][2] = mfma(ad[0][1], bv0, c1p);
+                        stage1(0, 1);
+                        half(0, 1, 1);
+                        slot_end();
+                        stage1(1, 1);
                         half(1, 1, 1);
                         slot_end();
-                        sv[0][1] = mfma(ad[0][1], bvp, sv[0][1]);
+                        stage1(0, 2);
                         cvt(0, 0);
                         if (s2) mk_c2x(xb, 0);
                         slot_end();
-                        sv[1][2] = mfma(ad[1][1], bv0, c1p);
+                        stage1(1, 2);
                         cvt(1, 0);
                         if (s2) mk_c2x(xb, 1);
-                        slot_end();
-                        sv[1][1] = mfma(ad[1][1], bvp, sv[1][1]);
-                        cvt(0, 2);
                         slot_end();
                         if (s2) stage2(0, 0);
                         cvt(0, 1);
                         slot_end();
                         if (s2) stage2(0, 1);
-                        cvt(1, 2);
+                        cvt(1, 1);
                         if (cb + 1 < 4) mk_keep(cb + 1, 0);
                         slot_end();
-                        if (s2) stage2(2, 0);
-                        cvt(1, 1);
+                        if (s2) stage2(1, 0);
+                        cvt(0, 2);
                         if (cb + 1 < 4) mk_keep(cb + 1, 1);
+                        slot_end();
+                        if (s2) stage2(1, 1);
+                        cvt(1, 2);
                         slot_end();
                         if (cb + 1 < 4) fetch(cb + 1, 0);
                         if (s2) {
-                            stage2(1, 0);
-                            slot_end();
-                            stage2(2, 1);
+                            stage2(2, 0);
                             mins(0, xb, o[0][0], o[1][0]);
                             slot_end();
-                            stage2(1, 1);
+                            stage2(2, 1);
                             slot_end();
-                            mins(2, xb, o[0][2], o[1][2]);
+                            mins(1, xb, o[0][1], o[1][1]);
                             slot_end();
-                            om[0] = o[0][1];
-                            om[1] = o[1][1];
+                            om[0] = o[0][2];
+                            om[1] = o[1][2];
                         }
                     } else {
                         // the last output block: both halves of t are there; the next pass's addresses go under its
@@ -657,23 +689,23 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
                         mk_c2x(xb, 1);
                         stage2(0, 1);
                         slot_end();
-                        stage2(2, 0);
-                        mins(1, xb - 1, om[0], om[1]);
-                        slot_end();
-                        stage2(2, 1);
-                        slot_end();
                         stage2(1, 0);
-                        mins(0, xb, o[0][0], o[1][0]);
+                        mins(2, xb - 1, om[0], om[1]);
                         slot_end();
                         stage2(1, 1);
                         slot_end();
-                        mins(2, xb, o[0][2], o[1][2]);
+                        stage2(2, 0);
+                        mins(0, xb, o[0][0], o[1][0]);
                         slot_end();
-                        om[0] = o[0][1];
-                        om[1] = o[1][1];
+                        stage2(2, 1);
+                        slot_end();
+                        mins(1, xb, o[0][1], o[1][1]);
+                        slot_end();
+                        om[0] = o[0][2];
+                        om[1] = o[1][2];
                     }
                 }
-                mins(1, NXB - 1, om[0], om[1]);
+                mins(2, NXB - 1, om[0], om[1]);
                 // (after the last MFMA that reads them: a write under it would wait for its C operand)
                 c2[0] += two;
                 c2[1] += two;
@@ -789,8 +821,8 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
         if (!prefetch) {   // an edge tile: the guarded loads, now
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                pw[i] = ld_image_u32(ce.right ? Rf : Lf, y0 - R + 8 * ce.q + i, (ce.right ? nxr : nxl) + ce.dx, W, H,
-                               a.pitch);
+                pw[i] = ld_image_u32(ce.right ? Rf : Lf, y0 - R + staged_row(ce.q, i), (ce.right ? nxr : nxl) + ce.dx,
+                                     W, H, a.pitch);
         }
         stage_pack(pw, ce.right ? rsm : lsm, ce.col, ce.q);
     }
