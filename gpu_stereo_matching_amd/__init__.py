@@ -196,6 +196,15 @@ class BlockMatcher:
     def set_guided_eps(self, eps: float):
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_GUIDED_EPS, float(eps)))
 
+    def set_workspace_poison(self, byte=None):
+        """A debugging aid (SM_PARAM_WORKSPACE_POISON): with byte in 0..255 every call first fills the handle's shared
+        workspaces it takes, and the frame buffers a host call uploads into, with that byte, so that no result can
+        depend on what an earlier call left there; one fill of each workspace per call.  None (the default) turns it
+        off.  Results are the same under every byte; other values are refused and change nothing."""
+        # (the parameter's 0 is "off" and v = byte + 1 otherwise; a negative byte must not arrive as 0)
+        v = 0.0 if byte is None else float(byte) + 1.0 if byte >= 0 else -1.0
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_WORKSPACE_POISON, v))
+
     def set_sgm_penalties(self, p1: int = 0, p2: int = 0):
         """Penalties of agg='sgm' (SM_PARAM_SGM_P1 / _P2): integers, 0 = auto (8 win^2 / 32 win^2 of the
         call's window).  P1 <= P2 and 255 win^2 + P2 <= 65535 are checked by the matching call."""

@@ -43,6 +43,7 @@ SM_PARAM_BOX_QUEUE_WORKGROUPS = 12
 SM_PARAM_SGM_PATHS = 13
 SM_PARAM_MIN_DISP = 14
 SM_PARAM_SUBPIX_MEDIAN = 15
+SM_PARAM_WORKSPACE_POISON = 16   # debugging aid: 0 off, v in 1..256 fills every workspace a call takes with byte v - 1
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED = (

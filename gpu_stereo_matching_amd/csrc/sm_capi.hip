@@ -75,6 +75,11 @@ hipError_t copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size
 int upload_pair(sm_handle* h, const uint8_t* left, const uint8_t* right, int W, int H, int pitch, hipStream_t s,
                 uint8_t** right_dev) {
     const int64_t P = (int64_t)W * H;
+    if (h->ws_poison) {   // SM_PARAM_WORKSPACE_POISON: the frame buffers over all they were allocated with (sm_create)
+        const size_t Pmax = (size_t)h->max_w * h->max_h;
+        SM_HIP(hipMemsetAsync(h->d_left, h->ws_poison - 1, 2 * align256(Pmax), s));   // d_right lies in it
+        SM_HIP(hipMemsetAsync(h->d_disp, h->ws_poison - 1, Pmax, s));
+    }
     static const bool pair_copy = env_switch("SM_PAIR_COPY", true);   // 0 (A/B only): always two copies
     // a pair with the right frame right after the left one (one sm_host_alloc block of 2 frames, or any
     // contiguous (2, H, W) array) goes up as one copy into d_left .. d_left + 2P: one DMA transfer
@@ -703,6 +708,15 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
             return fail(SM_ERR_INVALID_ARG,
                         "SM_PARAM_SUBPIX_MEDIAN: the sub-pixel median's radius must be an integer in [0, 3] (0 = off)");
         h->subpix_median = v;
+        return SM_OK;
+    }
+    if (param == SM_PARAM_WORKSPACE_POISON) {
+        const int v = (int)value;
+        if (!(value >= 0.f) || value > 256.f || (float)v != value)
+            return fail(SM_ERR_INVALID_ARG,
+                        "SM_PARAM_WORKSPACE_POISON: %g is no integer in [0, 256] (0 = off, v = fill with byte v - 1); "
+                        "it stays %d", (double)value, h->ws_poison);
+        h->ws_poison = v;
         return SM_OK;
     }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);

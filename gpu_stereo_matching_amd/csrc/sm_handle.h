@@ -129,6 +129,9 @@ struct sm_handle {
     int fill_gap = 0;            // SM_PARAM_FILL_GAP: 0 off, else the longest run of a row the matching calls fill
     int min_disp = 0;            // SM_PARAM_MIN_DISP: what plane 0 of a cost volume stands for (SM_PAIRS_IN_VIEW calls)
     int subpix_median = 0;       // SM_PARAM_SUBPIX_MEDIAN: 0 off, 1..3 the sub-pixel calls' median radius (bm_median16.hip)
+    // SM_PARAM_WORKSPACE_POISON: 0 off, v in 1..256 every call first fills the workspaces it takes (WsScope::get)
+    // and the frame buffers it uploads into (upload_pair) with byte v - 1
+    int ws_poison = 0;
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -180,7 +183,9 @@ class WsScope {
     int get(SharedBuf& b, size_t bytes, T** out) {
         *out = nullptr;
         int rc = touch();
+        const uint8_t* before = b.b_.p;
         if (!rc) rc = b.b_.reserve(bytes);
+        if (!rc && h_->ws_poison) rc = poison(b, b.b_.p != before);
         if (!rc) *out = b.b_.as<T>();
         return rc;
     }
@@ -201,9 +206,25 @@ class WsScope {
     }
 
   private:
+    // SM_PARAM_WORKSPACE_POISON: the whole of b, slack included, filled on s_ when this scope first takes it, and
+    // again when a later get had to grow it (the new block holds none of the call's data).  A second get of a
+    // buffer that stays where it is leaves the call's live data alone.
+    int poison(SharedBuf& b, bool regrown) {
+        const SharedBuf* const all[] = {&h_->lr, &h_->rpart, &h_->vol, &h_->spk, &h_->boxq};
+        unsigned bit = 0;
+        for (unsigned i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+            if (all[i] == &b) bit = 1u << i;
+        if ((poisoned_ & bit) && !regrown) return SM_OK;
+        poisoned_ |= bit;
+        if (b.b_.cap + b.b_.slack == 0) return SM_OK;
+        SM_HIP(hipMemsetAsync(b.b_.p, h_->ws_poison - 1, b.b_.cap + b.b_.slack, s_));
+        return SM_OK;
+    }
+
     sm_handle* h_;
     hipStream_t s_;
     bool used_ = false, drained_ = false;
+    unsigned poisoned_ = 0;   // the handle's shared buffers this scope has filled
 };
 
 // ---- argument checks (sm_capi.hip; the cost rules in sm_capi_volume.hip) ----

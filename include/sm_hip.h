@@ -208,11 +208,20 @@ enum {
                                   SM_ERR_INVALID_ARG; d0 >= width is legal and gives the all-zero map.  With d0 > 0 every
                                   matching call without SM_PAIRS_IN_VIEW is refused, naming the parameter (the
                                   segment-tree calls aside, which have no disparity window of this kind) */
-    SM_PARAM_SUBPIX_MEDIAN = 15 /* radius of the 16-bit median the sub-pixel calls run on both views' 1/16-px maps
+    SM_PARAM_SUBPIX_MEDIAN = 15, /* radius of the 16-bit median the sub-pixel calls run on both views' 1/16-px maps
                                   before the LR check: an integer 0..3, 0 (default) = off; other values:
                                   SM_ERR_INVALID_ARG, and the parameter keeps its value.  Read by sm_match_subpix_device,
                                   sm_block_match_subpix_u16 and sm_volume_wta_subpix_device alone (see "sub-pixel
                                   disparities" and "16-bit median" below); every other call ignores it */
+    SM_PARAM_WORKSPACE_POISON = 16 /* a debugging aid: 0 (default) = off; an integer v in 1..256 makes every call fill
+                                  each of the handle's shared workspaces it takes (whole capacity and slack, once per
+                                  call, before its first kernel) and the frame buffers a host call uploads into (their
+                                  whole allocation, before the copies) with byte v - 1, so that no result can depend on
+                                  what an earlier call or a fresh allocation left there.  No result changes under any
+                                  v; the cost is one fill of each workspace per call.  Off, nothing is enqueued.  The
+                                  other staging buffers of the host calls and the segment-tree workspace are not
+                                  filled.  Other values: SM_ERR_INVALID_ARG, and the parameter keeps its value, which
+                                  the error text names */
 };
 
 typedef struct sm_handle sm_handle;
