@@ -98,6 +98,14 @@ def census_workspace_bytes(width: int, height: int, num_disp: int, radius: int, 
     return n.value
 
 
+def guided_workspace_bytes(width: int, height: int, num_disp: int, radius: int) -> int:
+    """Bytes of the volume workspace one agg='guided' frame of the sub-pixel calls takes on its handle
+    (sm_guided_workspace_bytes, host-only): the uint32 costs and the LR check's planes."""
+    n = ctypes.c_size_t()
+    _capi.check(_capi.load().sm_guided_workspace_bytes(width, height, num_disp, radius, ctypes.byref(n)))
+    return n.value
+
+
 def speckle_workspace_bytes(width: int, height: int, batch: int = 1) -> int:
     """Bytes of device workspace the speckle filter takes on its handle for `batch` frames (uint32 labels and
     counts, 8 B per pixel of the up to 8 frames in flight; sm_speckle_workspace_bytes, host-only)."""
@@ -474,6 +482,39 @@ class BlockMatcher:
                                               out.ctypes.data))
         return out
 
+    def guided_volume(self, left, right, radius: int, num_disp: int) -> np.ndarray:
+        """The guided-filtered cost volume (sm_guided_volume_i32): int32 [num_disp, H, W], d-major,
+        trunc(q(d) * 2^14) with q clamped to [-512, 512), the cost field of a one-disparity guided slice key;
+        INT32_MAX where d > W - x.  One pass over all d; the handle's guided eps applies."""
+        L = _as_u8_image(left, "left")
+        R = _as_u8_image(right, "right")
+        if L.shape != R.shape:
+            raise ValueError("left/right sizes differ")
+        H, W = L.shape
+        out = np.empty((num_disp, H, W), np.int32)
+        _capi.check(self._lib.sm_guided_volume_i32(self._h, L.ctypes.data, R.ctypes.data, W, H, W, radius, num_disp,
+                                                   out.ctypes.data))
+        return out
+
+    def guided_volume_device(self, left_t, right_t, radius: int, num_disp: int, out_t=None, stream=None):
+        """Device form of :meth:`guided_volume` (sm_guided_volume_device): [H, W] uint8 cuda tensors whose rows may
+        be strided (stride(1) == 1, one row stride for both); int32 [num_disp, H, W] out, async on `stream`."""
+        import torch
+        if left_t.dtype != torch.uint8 or right_t.dtype != torch.uint8 or left_t.dim() != 2 \
+                or left_t.shape != right_t.shape or not (left_t.is_cuda and right_t.is_cuda) \
+                or left_t.stride(1) != 1 or right_t.stride(1) != 1 or left_t.stride(0) != right_t.stride(0):
+            raise ValueError("expected two [H, W] uint8 device tensors of one shape and row stride")
+        if left_t.device != right_t.device or left_t.device.index != self.device:
+            raise ValueError(f"frames must be on cuda:{self.device}, the handle's device")
+        H, W = left_t.shape
+        if out_t is None:
+            out_t = torch.empty((num_disp, H, W), dtype=torch.int32, device=left_t.device)
+        _check_out(out_t, (num_disp, H, W), torch.int32, left_t.device)
+        _capi.check(self._lib.sm_guided_volume_device(self._h, left_t.data_ptr(), right_t.data_ptr(), W, H,
+                                                      left_t.stride(0), radius, num_disp, out_t.data_ptr(),
+                                                      self._stream_ptr(stream)))
+        return out_t
+
     def census_volume(self, left, right, num_disp: int) -> np.ndarray:
         """The Hamming volume of the census cost (sm_census_volume_u8): uint8 [num_disp, H, W], d-major,
         popcount(censusL(y, x) ^ censusR(y, x - d)) for x >= d, 0 where x < d."""
@@ -690,6 +731,11 @@ class BlockMatcher:
         invalid when a disparity more than 1 away from its best costs less than best * 100 / (100 - u)."""
         _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_UNIQUENESS, float(u)))
 
+    def set_guided_subpix(self, on: bool = True):
+        """SM_PARAM_GUIDED_SUBPIX: on, match_subpix and match_subpix_device take agg='guided' and build the guided
+        cost volume per frame; off (the default) they refuse it, as they did before that volume existed."""
+        _capi.check(self._lib.sm_set_param_f(self._h, _capi.SM_PARAM_GUIDED_SUBPIX, 1.0 if on else 0.0))
+
     def set_subpix_median(self, radius=0):
         """The 16-bit median of the sub-pixel calls (SM_PARAM_SUBPIX_MEDIAN): with radius 1..3, match_subpix,
         match_subpix_device and volume_wta_subpix_device filter both views' 1/16-px maps with the (2r+1)^2 median
@@ -739,7 +785,8 @@ class BlockMatcher:
                      pairs: str = "reference"):
         """uint16 [H, W] disparity in 1/16 px (sm_block_match_subpix_u16): 16 * d + a parabola fit through the
         costs next to the best d, 0 where the pixel is invalid (uniqueness, the AD box threshold) or occluded
-        (lr_check).  agg 'box' or 'sgm', cost 'ad' or 'census', radius <= 7.  pairs='in-view': SM_PAIRS_IN_VIEW with
+        (lr_check).  agg 'box', 'sgm' or, after set_guided_subpix(), 'guided' (the guided volume in one pass, invalid
+        where q >= 50; cost 'ad', reference pairs and uniqueness 0 only), cost 'ad' or 'census', radius <= 7.  pairs='in-view': SM_PAIRS_IN_VIEW with
         the handle's minimum disparity, values up to 16 * 4095 + 8.  return_right / return_mask: a tuple
         (map[, right-view map][, uint8 valid mask])."""
         L = _as_u8_image(left, "left")

@@ -43,6 +43,7 @@ SM_PARAM_BOX_QUEUE_WORKGROUPS = 12
 SM_PARAM_SGM_PATHS = 13
 SM_PARAM_MIN_DISP = 14
 SM_PARAM_SUBPIX_MEDIAN = 15
+SM_PARAM_GUIDED_SUBPIX = 17      # 1: the sub-pixel calls accept SM_AGG_GUIDED (the one-pass guided volume); 0: they refuse it
 SM_PARAM_WORKSPACE_POISON = 16   # debugging aid: 0 off, v in 1..256 fills every workspace a call takes with byte v - 1
 
 # every symbol include/sm_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -67,6 +68,7 @@ EXPORTED = (
     "sm_speckle_workspace_bytes", "sm_speckle_filter_device", "sm_speckle_filter_u8", "sm_speckle_filter_u16",
     "sm_fill_invalid_device", "sm_fill_invalid_u8", "sm_fill_invalid_u16",
     "sm_median_u16_device", "sm_median_u16",
+    "sm_guided_volume_device", "sm_guided_volume_i32", "sm_guided_workspace_bytes",
 )
 
 
@@ -170,6 +172,9 @@ def load(path: str = LIB_PATH):
     L.sm_fill_invalid_u16.argtypes = [vp, vp, i, i, i, i]
     L.sm_median_u16_device.argtypes = [vp, vp, i, i, i, i, i64, i, vp, i, i64, vp]
     L.sm_median_u16.argtypes = [vp, vp, i, i, i, i, vp, i]
+    L.sm_guided_volume_device.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
+    L.sm_guided_volume_i32.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+    L.sm_guided_workspace_bytes.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_size_t)]
     for name in EXPORTED:
         if name not in ("sm_version", "sm_last_error_string"):
             getattr(L, name).restype = ctypes.c_int

@@ -43,6 +43,23 @@ struct GuidedPass {
 // starts at d_lo = 0, and the right view is all or nothing: gpart with right_map beside disp or right_keys beside keys
 hipError_t launch_guided(const GuidedPass& p, hipStream_t s);
 
+// The guided cost volume of one frame in one pass: the guide statistics once per tile, every d's cost stored
+// (bm_guided_plan.h: the planes' values).
+struct GuidedVolumePass {
+    const uint8_t* left;    // [H][pitch]
+    const uint8_t* right;
+    int W, H, pitch;
+    int radius;             // 0..kMaxGuidedRadius
+    int num_disp;           // 1..kMaxGuidedDisp
+    float eps;
+    // [num_disp][H][W] dense: int32 trunc(q * 2^14), INT32_MAX where d > W - x; biased: uint32, that cost +
+    // kGuidedVolumeBias, kGuidedVolumeNone where d > W - x
+    void* vol;
+    bool biased;
+};
+// hipErrorInvalidValue unless guided_volume_ok holds, the pointers are set and pitch >= W
+hipError_t launch_guided_volume(const GuidedVolumePass& p, hipStream_t s);
+
 // combined keys -> disparity with the Device.cu:37 threshold q < 50
 hipError_t launch_guided_keys_to_disp(const int* keys, int W, int H, uint8_t* disp, int out_pitch, hipStream_t s);
 

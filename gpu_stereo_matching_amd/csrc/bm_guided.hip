@@ -294,13 +294,28 @@ constexpr float kRightScaleSat = 4194304.0f;   // 2^22
 constexpr int kModeLeft = 0;        // valid d <= W - x, threshold 50 (Device.cu:37, :44); the map into disp
 constexpr int kModeMirrored = 1;    // valid d <= x, no threshold: unreachable since the right view was fused
 constexpr int kModeSliceKeys = 2;   // valid d <= W - x, no threshold; the slice's keys into keys
+constexpr int kGuidedVolumeVariant = 16;   // > kMaxGuidedRadius: the template argument R | 16 selects VOL
+// the volume kernel (VOL) alone: valid d <= W - x, no threshold, no WTA; every d's cost into plane d of keys
+constexpr int kModeVolume = 3;     // int32 trunc(q 2^14), the slice key's cost field; INT32_MAX where d > W - x
+constexpr int kModeVolumeU24 = 4;   // uint32 trunc(q 2^14) + 2^23 < 2^24; kGuidedVolumeNone where d > W - x
 
 // The pass over d in [d_lo, d_hi); K: the right-key chain's steps (RIGHT)
-template <int R, bool RIGHT>
-__global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fused_kernel(
+// VOL (left-only, one frame, d_lo = 0): the cost volume instead of the map.  S2H stores the cost of every output at
+// every d where the other modes keep a running minimum: plane d of keys, [d][H][W] dense.  It is the slice key's cost
+// field bit for bit: the same S1V .. S2H floats (the same GeoF, roles and segments as the left-only kernel), the
+// same scale 2^14 / N, clamp and truncation as the kModeSliceKeys epilogue.  S2H takes the right view's lane
+// layout, lane = segment + 8 * row, so the 8 lanes of a row write one contiguous run of TW dwords per d.
+// The volume kernel is the instantiation RV = R | kGuidedVolumeVariant of the same template: the kernels of the maps
+// keep their two template arguments, so their symbols and their machine code are what they were (the counters of
+// profiles/valu_counts.json are stamped with both).
+template <int RV, bool RIGHT>
+__global__ __launch_bounds__(kT, (kGuidedWavesPerEU<(RV & (kGuidedVolumeVariant - 1)), RIGHT>)) void guided_fused_kernel(
     const uint8_t* __restrict__ Limg, const uint8_t* __restrict__ Rimg, int W, int H, int pitch, int64_t fstride,
     int d_lo, int d_hi, float eps, int mode, uint8_t* __restrict__ disp, int out_pitch, int64_t ostride,
     int tiles_x, int tiles, int* __restrict__ gpart, int K, int* __restrict__ keys) {
+    constexpr int R = RV & (kGuidedVolumeVariant - 1);
+    constexpr bool VOL = (RV & kGuidedVolumeVariant) != 0;
+    static_assert(R <= kMaxGuidedRadius && !(RIGHT && VOL), "the volume kernel is left-only");
     constexpr bool ROLES = kGuidedRoles<R, RIGHT>;
     // the right view with the roles needs S2H's per-output state in fewer registers: I as f16 pairs read
     // by v_fma_mix_f32 (the same single-rounding fma, so the same maps; issued as VOP3P it costs more than
@@ -393,8 +408,8 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     // key chain runs from each segment to the next lane: lane = segment + 8 * row.
     // With the right view, the 32-lane half-wave G = tid >> 5 holds rows {G, G + TH/4, G + TH/2, G + 3TH/4}
     // (8 segments each) so that its b64 reads of the mm planes fall on distinct bank pairs.
-    const int h2r = RIGHT ? (((tid >> 3) & 3) * (G::TH / 4) + (tid >> 5)) : (tid % G::TH);
-    const int h2s = RIGHT ? (tid & 7) : (tid / G::TH);
+    const int h2r = (RIGHT || VOL) ? (((tid >> 3) & 3) * (G::TH / 4) + (tid >> 5)) : (tid % G::TH);
+    const int h2s = (RIGHT || VOL) ? (tid & 7) : (tid / G::TH);
     // S2H's mm row segment (plane A) as an LDS byte address; plane B is MM_PLANE bytes further
     const uint32_t h2off = (uint32_t)(G::CS_BYTES + (h2r * G::MSA + h2s * G::SW2) * 4);
     // S2V's first mm row of this wave (plane A), for the add-TID stores
@@ -421,6 +436,13 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     // keys then clamp to the maximum), and the key slots
     float rinv[RIGHT ? G::SW2 : 1];
     int rk[RIGHT ? G::SW2 : 1];
+    // volume kernel: 2^14 / N per output, the outputs this thread stores (bit o), its row segment in plane 0
+    float vs[VOL ? G::SW2 : 1];
+    uint32_t vok = 0u;
+    int* const vrow = VOL ? keys + (int64_t)oy * W + x0 + h2s * G::SW2 : nullptr;
+    const int64_t vplane = (int64_t)W * H;
+    const int vnone = mode == kModeVolumeU24 ? (int)kGuidedVolumeNone : INT_MAX;
+    const int vbias = mode == kModeVolumeU24 ? (int)kGuidedVolumeBias : 0;
 #pragma unroll
     for (int o = 0; o < G::SW2; ++o) {
         const int x = x0 + h2s * G::SW2 + o;
@@ -440,6 +462,10 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
             rinv[o] = ok ? kRightScaleSat / (float)(win_count(x, R, W) * win_count(oy, R, H))
                          : __builtin_nanf("");
             rk[o] = INT_MAX;
+        }
+        if constexpr (VOL) {
+            vs[o] = kRightScale / (float)(win_count(x, R, W) * win_count(oy, R, H));
+            vok |= ok ? 1u << o : 0u;
         }
     }
 
@@ -669,9 +695,16 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
                 q = sa * oI[o] + sb;
                 valid = d <= dlim[o];
             }
-            const bool take = (!LIM || valid) && q < bq[o];
-            bq[o] = take ? q : bq[o];
-            bdd[o] = take ? d : bdd[o];
+            if constexpr (VOL) {
+                // the kModeSliceKeys epilogue on this d alone; only outputs inside the image and the tile store
+                const float qs = __builtin_fmaxf(__builtin_fminf(q * vs[o], kRightMax), kRightMin);
+                const int cost = (!LIM || valid) && q < __builtin_huge_valf() ? (int)qs + vbias : vnone;
+                if (vok >> o & 1u) vrow[(int64_t)d * vplane + o] = cost;
+            } else {
+                const bool take = (!LIM || valid) && q < bq[o];
+                bq[o] = take ? q : bq[o];
+                bdd[o] = take ? d : bdd[o];
+            }
             if constexpr (RIGHT) {
                 // candidate for right pixel u = x - d (slot o): q = (N q) / N, fixed point, position
                 // 7 SW2 + o (the output column relative to this segment, see the file header).
@@ -727,6 +760,7 @@ __global__ __launch_bounds__(kT, (kGuidedWavesPerEU<R, RIGHT>)) void guided_fuse
     if constexpr (RIGHT) {
         for (int k = d_hi; k < d_lo + K; ++k) chain_step(k);
     }
+    if constexpr (VOL) return;
     if (mode == kModeSliceKeys) {
         // d-slice keys: (q * 2^14 << 8) | d, INT_MAX where no d of the slice is valid
         int* Kf = keys + (int64_t)frame * H * W;
@@ -882,6 +916,23 @@ hipError_t launch_guided(const GuidedPass& p, hipStream_t s) {
     if ((p.gpart != nullptr) != (p.right_map != nullptr || p.right_keys != nullptr)) return hipErrorInvalidValue;
     return with_radius<0, kMaxFastRadius>(p.radius, hipErrorInvalidValue,
                                           [&](auto r) { return run_fused<decltype(r)::value>(p, s); });
+}
+
+hipError_t launch_guided_volume(const GuidedVolumePass& p, hipStream_t s) {
+    if (!guided_volume_ok(p.W, p.H, p.radius, p.num_disp) || !p.left || !p.right || !p.vol || p.pitch < p.W)
+        return hipErrorInvalidValue;
+    return with_radius<0, kMaxFastRadius>(p.radius, hipErrorInvalidValue, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        constexpr int TW = guided_tile_w(R), TH = kGuidedTileH;
+        const int tiles_x = (p.W + TW - 1) / TW, tiles_y = (p.H + TH - 1) / TH;
+        if ((int64_t)tiles_x * tiles_y > 0x7FFFFFFF) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((guided_fused_kernel<(R | kGuidedVolumeVariant), false>),
+                           dim3((unsigned)(tiles_x * tiles_y)), dim3(kT), (GeoF<R, kGuidedRoles<R, false>>::LDS), s,
+                           p.left, p.right, p.W, p.H, p.pitch, (int64_t)0, 0, p.num_disp, p.eps,
+                           p.biased ? kModeVolumeU24 : kModeVolume, nullptr, 0, (int64_t)0, tiles_x, tiles_x * tiles_y,
+                           nullptr, 0, static_cast<int*>(p.vol));
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_guided_keys_to_disp(const int* keys, int W, int H, uint8_t* disp, int out_pitch, hipStream_t s) {

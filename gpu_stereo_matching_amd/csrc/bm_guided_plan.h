@@ -48,4 +48,21 @@ inline bool guided_pass_ok(int W, int H, int radius, int d_lo, int d_hi, int bat
            H > 0 && batch > 0;
 }
 
+// ---- the cost volume (launch_guided_volume): every d's cost kept, [D][H][W] dense 32-bit planes ----
+// A cost is trunc(q * 2^14) with q clamped to [-512, 512): a signed 24-bit value, the cost field of a slice key.  The
+// biased form adds 2^23, so every cost is a uint32 below 2^24, the bound of the sub-pixel WTA (bm_subpix.hip); the
+// threshold q < 50 of the 8-bit guided map becomes V < kGuidedInvalidFrom.  A pair that does not exist (d > W - x)
+// holds INT32_MAX, or biased the largest cost: it never beats a pair that exists (d = 0 always does, and the WTA
+// keeps the first minimum), and it keeps the WTA's arithmetic inside its bound where the right view walks over it.
+constexpr int kGuidedCostShift = 14;
+constexpr uint32_t kGuidedVolumeBias = 512u << kGuidedCostShift;            // 2^23
+constexpr uint32_t kGuidedVolumeNone = 2u * kGuidedVolumeBias - 1u;          // 2^24 - 1
+constexpr uint32_t kGuidedInvalidFrom = (50u + 512u) << kGuidedCostShift;   // q >= 50: no match
+static_assert(kGuidedVolumeNone < (1u << 24) && kGuidedInvalidFrom < kGuidedVolumeNone, "V < 2^24 (bm_subpix.hip)");
+
+inline size_t guided_volume_bytes(int W, int H, int D) { return (size_t)4 * (size_t)W * (size_t)H * (size_t)D; }
+
+// what launch_guided_volume takes: one frame, d in [0, D)
+inline bool guided_volume_ok(int W, int H, int radius, int D) { return guided_pass_ok(W, H, radius, 0, D, 1); }
+
 }  // namespace sm

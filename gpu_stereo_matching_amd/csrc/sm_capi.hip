@@ -719,6 +719,13 @@ SM_API int sm_set_param_f(sm_handle* h, int param, float value) {
         h->ws_poison = v;
         return SM_OK;
     }
+    if (param == SM_PARAM_GUIDED_SUBPIX) {
+        if (value != 0.f && value != 1.f)
+            return fail(SM_ERR_INVALID_ARG, "SM_PARAM_GUIDED_SUBPIX: %g is neither 0 (off) nor 1 (on); it stays %d",
+                        (double)value, h->guided_subpix);
+        h->guided_subpix = (int)value;
+        return SM_OK;
+    }
     return fail(SM_ERR_INVALID_ARG, "unknown param %d", param);
 }
 

@@ -184,6 +184,53 @@ int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, in
     return SM_OK;
 }
 
+// ---- SM_AGG_GUIDED in the sub-pixel calls (bm_guided.hip: launch_guided_volume) ----
+// Per frame: the guided costs of every d in one pass, biased to uint32 V = trunc(q 2^14) + 2^23 < 2^24, into the head
+// of the volume workspace; then run_volume's sub-pixel step on V with the 8-bit guided call's rule: left view
+// d <= min(D - 1, W - x) and invalid where q >= 50 (V >= kGuidedInvalidFrom), right view V_R(u, d) = V(u + d, d)
+// over u + d < W without a threshold, no uniqueness (subpix_check).  The right view's walk crosses entries with
+// d > W - x, which hold the largest cost (bm_guided_plan.h).
+int run_guided_subpix(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
+                      int64_t fstride, int radius, int D, const VolumeOut& o) {
+    const int64_t P = (int64_t)W * H;
+    const VolumeLayout w = guided_volume_layout(P, D);
+    hipStream_t s = ws.stream();
+    uint8_t* vol = nullptr;
+    const int rc = ws.get(h->vol, w.bytes, &vol);   // before any launch
+    if (rc) {
+        const std::string why = g_err;
+        return fail(rc, "sub-pixel SM_AGG_GUIDED: no %zu-byte workspace for %dx%d D=%d (sm_guided_workspace_bytes): %s",
+                    w.bytes, W, H, D, why.c_str());
+    }
+    const int med = h->subpix_median;
+    SubpixMedianWs mw;
+    if (med) {
+        uint8_t* planes = nullptr;
+        const int rc2 = ws.get(h->lr, subpix_median_bytes(P, o.lr, o.right16 != nullptr), &planes);
+        if (rc2) return rc2;
+        mw = subpix_median_ws(planes, P, o.lr, o.right16 != nullptr);
+    }
+    const uint32_t* V = reinterpret_cast<const uint32_t*>(vol);
+    const sm::Pairs pr;
+    for (int f = 0; f < batch; ++f) {
+        const sm::GuidedVolumePass g{L + f * fstride, R + f * fstride, W, H, pitch, radius, D, h->guided_eps, vol, true};
+        SM_HIP(sm::launch_guided_volume(g, s));
+        uint16_t* out = o.disp16 + f * o.ostride;
+        uint16_t* rout = o.right16 ? o.right16 + f * P : nullptr;
+        uint8_t* mout = o.mask ? o.mask + f * P : nullptr;
+        if (med) {   // both views unchecked into the planes, then median -> check on the filtered maps -> mask
+            SM_HIP(sm::launch_subpix_wta_u32(V, W, H, D, sm::kGuidedInvalidFrom, 0, 2, false, mw.left, W, mw.right,
+                                             nullptr, nullptr, s, pr));
+            const int rc2 = run_subpix_median(s, mw, W, H, med, out, o.opitch, rout, o.lr, mout);
+            if (rc2) return rc2;
+            continue;
+        }
+        SM_HIP(sm::launch_subpix_wta_u32(V, W, H, D, sm::kGuidedInvalidFrom, 0, 2, o.lr, out, o.opitch, rout, mout,
+                                         vol + w.rkeys, s, pr));
+    }
+    return SM_OK;
+}
+
 }  // namespace smh
 
 using namespace smh;
@@ -200,10 +247,16 @@ int subpix_check(const sm_handle* h, int width, int height, int pitch, int radiu
         return fail(SM_ERR_INVALID_ARG,
                     "sub-pixel: SM_MEDIAN is not supported (the flag is the 8-bit ctmf median; the 1/16-px maps take "
                     "the 16-bit median of SM_PARAM_SUBPIX_MEDIAN)");
-    if (flags & (SM_AGG_GUIDED | SM_STAGED | SM_DEVICE_CU_GRID))
+    // SM_AGG_GUIDED builds its volume only on a handle that asked for it (SM_PARAM_GUIDED_SUBPIX); otherwise, and
+    // without a handle, it is refused as before the volume kernel existed
+    const bool guided = (flags & SM_AGG_GUIDED) != 0 && h && h->guided_subpix;
+    if (guided && (flags & (SM_STAGED | SM_DEVICE_CU_GRID)))
+        return fail(SM_ERR_INVALID_ARG,
+                    "sub-pixel: SM_AGG_GUIDED does not combine with SM_STAGED or SM_DEVICE_CU_GRID (flags 0x%x)", flags);
+    if ((flags & (SM_STAGED | SM_DEVICE_CU_GRID)) || ((flags & SM_AGG_GUIDED) && !guided))
         return fail(SM_ERR_INVALID_ARG,
                     "sub-pixel: SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID keep no cost volume to interpolate "
-                    "(flags 0x%x)", flags);
+                    "(flags 0x%x; SM_AGG_GUIDED builds one per frame on a handle with SM_PARAM_GUIDED_SUBPIX = 1)", flags);
     if (radius > sm::kMaxFastRadius)
         return fail(SM_ERR_INVALID_ARG, "sub-pixel: radius %d out of [0, %d] (the u16 cost volume)", radius,
                     sm::kMaxFastRadius);
@@ -214,7 +267,21 @@ int subpix_check(const sm_handle* h, int width, int height, int pitch, int radiu
     if (rc) return rc;
     if (flags & SM_AGG_SGM) return sgm_check(width, radius, flags, h->sgm_p1, h->sgm_p2, p1_out, p2_out);
     if (flags & SM_COST_CENSUS) return census_check(width, radius, flags);
+    // SM_AGG_GUIDED: in-view pairs, a minimum disparity, the census cost and SGM have been refused above
+    if (guided && h->uniqueness > 0)
+        return fail(SM_ERR_INVALID_ARG,
+                    "sub-pixel: SM_PARAM_UNIQUENESS %d does not combine with SM_AGG_GUIDED (flags 0x%x): the ratio "
+                    "test has no meaning on a cost that can be negative", h->uniqueness, flags);
     return SM_OK;
+}
+
+// The sub-pixel calls' pass by aggregation: the guided volume, or run_volume
+int run_subpix(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
+               int64_t fstride, int radius, int D, unsigned flags, int p1, int p2, const sm::Pairs& pr,
+               const VolumeOut& o) {
+    if (flags & SM_AGG_GUIDED) return run_guided_subpix(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, o);
+    return run_volume(ws, h, L, R, W, H, pitch, batch, fstride, radius, D, (flags & SM_AGG_SGM) != 0,
+                      (flags & SM_COST_CENSUS) != 0, p1, p2, pr, o);
 }
 
 // run_volume's last step for the sub-pixel calls: 1/16-px maps, the LR check with SM_LR_CHECK in `flags`
@@ -278,6 +345,65 @@ SM_API int sm_census_workspace_bytes(int width, int height, int num_disp, int ra
     return SM_OK;
 }
 
+// ---- the guided cost volume (bm_guided.hip: launch_guided_volume) ----
+namespace {
+// what both volume calls check before the device is touched: the slice-key call's geometry and radii
+int guided_volume_check(const sm_handle* h, int width, int height, int pitch, int radius, int num_disp) {
+    int rc = check_geometry(h, width, height, pitch, radius, num_disp);
+    if (rc) return rc;
+    rc = pairs_refuse(h, 0u, "the guided volume call");
+    if (rc) return rc;
+    return guided_radius_check(radius);
+}
+}  // namespace
+
+SM_API int sm_guided_workspace_bytes(int width, int height, int num_disp, int radius, size_t* bytes) {
+    if (!bytes) return fail(SM_ERR_INVALID_ARG, "null bytes pointer");
+    *bytes = 0;
+    if (width < 1 || width > 4096) return fail(SM_ERR_INVALID_ARG, "sub-pixel SM_AGG_GUIDED: width %d out of [1, 4096]", width);
+    if (height < 1) return fail(SM_ERR_INVALID_ARG, "bad frame height %d", height);
+    if (num_disp < 1 || num_disp > sm::kMaxDisp)
+        return fail(SM_ERR_INVALID_ARG, "num_disp %d out of [1,%d]", num_disp, sm::kMaxDisp);
+    if (radius < 0) return fail(SM_ERR_INVALID_ARG, "radius %d out of [0, %d]", radius, sm::kMaxGuidedRadius);
+    const int rc = guided_radius_check(radius);
+    if (rc) return rc;
+    *bytes = guided_volume_layout((int64_t)width * height, num_disp).bytes;
+    return SM_OK;
+}
+
+SM_API int sm_guided_volume_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
+                                   int pitch, int radius, int num_disp, int32_t* d_vol, void* stream) {
+    const int rc = guided_volume_check(h, width, height, pitch, radius, num_disp);
+    if (rc) return rc;
+    if (!d_left || !d_right || !d_vol) return fail(SM_ERR_INVALID_ARG, "null device pointer");
+    SM_HIP(hipSetDevice(h->device));
+    const sm::GuidedVolumePass g{d_left, d_right, width, height, pitch, radius, num_disp, h->guided_eps, d_vol, false};
+    SM_HIP(sm::launch_guided_volume(g, stream_of(stream)));
+    return SM_OK;
+}
+
+SM_API int sm_guided_volume_i32(sm_handle* h, const uint8_t* left, const uint8_t* right, int width, int height,
+                                int pitch, int radius, int num_disp, int32_t* vol_out) {
+    int rc = guided_volume_check(h, width, height, pitch, radius, num_disp);
+    if (rc) return rc;
+    if (!left || !right || !vol_out) return fail(SM_ERR_INVALID_ARG, "null image pointer");
+    rc = check_capacity(h, width, height, num_disp);
+    if (rc) return rc;
+    SM_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t need = sm::guided_volume_bytes(width, height, num_disp);
+    WsScope ws(h, s);
+    uint8_t* vol = nullptr;
+    rc = ws.get(h->vol, need, &vol);
+    if (rc) return rc;
+    rc = upload_pair(h, left, right, width, height, pitch, s);
+    if (rc) return rc;
+    const sm::GuidedVolumePass g{h->d_left, h->d_right, width, height, width, radius, num_disp, h->guided_eps, vol, false};
+    SM_HIP(sm::launch_guided_volume(g, s));
+    SM_HIP(hipMemcpyAsync(vol_out, vol, need, hipMemcpyDeviceToHost, s));
+    return ws.drain();
+}
+
 SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uint8_t* d_right, int width, int height,
                                   int pitch, int batch, int64_t frame_stride, int radius, int num_disp, unsigned flags,
                                   uint16_t* d_disp16, int out_pitch, int64_t out_frame_stride, uint16_t* d_right16,
@@ -293,9 +419,8 @@ SM_API int sm_match_subpix_device(sm_handle* h, const uint8_t* d_left, const uin
         return fail(SM_ERR_INVALID_ARG, "frame strides overlap");
     SM_HIP(hipSetDevice(h->device));
     WsScope ws(h, stream_of(stream));
-    rc = run_volume(ws, h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp,
-                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2, pr,
-                    subpix_out(d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, flags));
+    rc = run_subpix(ws, h, d_left, d_right, width, height, pitch, batch, frame_stride, radius, num_disp, flags, p1, p2,
+                    pr, subpix_out(d_disp16, out_pitch, out_frame_stride, d_right16, d_mask, flags));
     if (rc) return rc;
     return subpix_speckle(ws, h, d_disp16, width, height, out_pitch, batch, out_frame_stride, d_mask);
 }
@@ -322,9 +447,8 @@ SM_API int sm_block_match_subpix_u16(sm_handle* h, const uint8_t* left, const ui
     rc = upload_pair(h, left, right, width, height, pitch, s);
     if (rc) return rc;
     WsScope ws(h, s);
-    rc = run_volume(ws, h, h->d_left, h->d_right, width, height, width, 1, (int64_t)P, radius, num_disp,
-                    (flags & SM_AGG_SGM) != 0, (flags & SM_COST_CENSUS) != 0, p1, p2, pr,
-                    subpix_out(dq, width, (int64_t)P, right16_out ? dr : nullptr, mask_out ? dm : nullptr, flags));
+    rc = run_subpix(ws, h, h->d_left, h->d_right, width, height, width, 1, (int64_t)P, radius, num_disp, flags, p1, p2,
+                    pr, subpix_out(dq, width, (int64_t)P, right16_out ? dr : nullptr, mask_out ? dm : nullptr, flags));
     if (rc) return rc;
     rc = subpix_speckle(ws, h, dq, width, height, width, 1, (int64_t)P, mask_out ? dm : nullptr);
     if (rc) return rc;

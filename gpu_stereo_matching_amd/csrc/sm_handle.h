@@ -132,6 +132,7 @@ struct sm_handle {
     // SM_PARAM_WORKSPACE_POISON: 0 off, v in 1..256 every call first fills the workspaces it takes (WsScope::get)
     // and the frame buffers it uploads into (upload_pair) with byte v - 1
     int ws_poison = 0;
+    int guided_subpix = 0;       // SM_PARAM_GUIDED_SUBPIX: 1 the sub-pixel calls take SM_AGG_GUIDED, 0 they refuse it
     bool stage_requested = false;
     // The shared workspaces serve every call on the handle while calls run on the stream they are given: the
     // end of each pass that used one is recorded here, and a pass on another stream waits for it first, so two
@@ -321,6 +322,15 @@ inline VolumeLayout volume_layout(int64_t P, int D, bool sgm, bool census) {
     return w;
 }
 
+// SM_AGG_GUIDED in the sub-pixel calls: [biased u32 costs 4PD][the LR check's d0 planes, the rkeys region 4P]; no
+// u16 costs and no census words, so sad == rkeys and cl == cr == bytes
+inline VolumeLayout guided_volume_layout(int64_t P, int D) {
+    VolumeLayout w;
+    w.sad = w.rkeys = align256((size_t)(4 * P * D));
+    w.cl = w.cr = w.bytes = w.rkeys + align256((size_t)(4 * P));
+    return w;
+}
+
 // The last step of run_volume, by where its result goes: the 8-bit maps (left into lmap; right, when right_map
 // is given, into dense W x H planes), or with disp16 the 1/16-px maps of bm_subpix.hip (right16 / mask: dense
 // W x H planes or null; lr: the LR check runs).
@@ -340,6 +350,10 @@ struct VolumeOut {
 int run_volume(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
                int64_t fstride, int radius, int D, bool sgm, bool census, int p1, int p2, const sm::Pairs& pr,
                const VolumeOut& o);
+// SM_AGG_GUIDED in the sub-pixel calls (sm_capi_volume.hip): per frame the one-pass guided volume, biased, into the
+// volume workspace (guided_volume_layout), then run_volume's sub-pixel step on it.  o.disp16 is set.
+int run_guided_subpix(WsScope& ws, sm_handle* h, const uint8_t* L, const uint8_t* R, int W, int H, int pitch, int batch,
+                      int64_t fstride, int radius, int D, const VolumeOut& o);
 
 // ---- the box pass (sm_capi.hip) ----
 // Where the right view of a box pass goes, by what the plan was asked for.

@@ -213,7 +213,7 @@ enum {
                                   SM_ERR_INVALID_ARG, and the parameter keeps its value.  Read by sm_match_subpix_device,
                                   sm_block_match_subpix_u16 and sm_volume_wta_subpix_device alone (see "sub-pixel
                                   disparities" and "16-bit median" below); every other call ignores it */
-    SM_PARAM_WORKSPACE_POISON = 16 /* a debugging aid: 0 (default) = off; an integer v in 1..256 makes every call fill
+    SM_PARAM_WORKSPACE_POISON = 16, /* a debugging aid: 0 (default) = off; an integer v in 1..256 makes every call fill
                                   each of the handle's shared workspaces it takes (whole capacity and slack, once per
                                   call, before its first kernel) and the frame buffers a host call uploads into (their
                                   whole allocation, before the copies) with byte v - 1, so that no result can depend on
@@ -222,6 +222,11 @@ enum {
                                   other staging buffers of the host calls and the segment-tree workspace are not
                                   filled.  Other values: SM_ERR_INVALID_ARG, and the parameter keeps its value, which
                                   the error text names */
+    SM_PARAM_GUIDED_SUBPIX = 17 /* 1: sm_match_subpix_device and sm_block_match_subpix_u16 accept SM_AGG_GUIDED and
+                                  build the guided cost volume per frame (see "sub-pixel disparity" below); 0
+                                  (default): they refuse the flag, as they did before the volume kernel existed, so a
+                                  caller that relies on the refusal keeps it.  Other values: SM_ERR_INVALID_ARG, and the
+                                  parameter keeps its value.  Every other call ignores it */
 };
 
 typedef struct sm_handle sm_handle;
@@ -330,6 +335,24 @@ SM_API int sm_guided_slice_keys_device(sm_handle *h, const uint8_t *d_left, cons
 SM_API int sm_guided_keys_to_disp_device(sm_handle *h, const int32_t *d_keys, int width, int height,
                                          uint8_t *d_disp, int out_pitch, void *stream);
 
+/* ---- the guided cost volume, one pass (SM_AGG_GUIDED) ----
+ * vol[d][y][x] = (int32)trunc(q(d) * 2^14), q the guided-filtered cost of pixel (y, x) at disparity d clamped to
+ * [-512, 512): the cost field of sm_guided_slice_keys_device's key for the slice [d, d + 1), key >> 8 (arithmetic),
+ * bit for bit, for every d in [0, num_disp) from one launch that computes the guide statistics once per tile
+ * instead of once per d.  INT32_MAX where the pair does not exist (d > width - x).  d-major dense planes
+ * [num_disp][height][width].  The radii (<= 7), sizes and the handle's SM_PARAM_GUIDED_EPS are the slice call's; a
+ * handle with SM_PARAM_MIN_DISP > 0 is refused (plane 0 is d = 0).
+ * sm_guided_volume_device: d_vol holds 4 * num_disp * width * height bytes; asynchronous on `stream`, no workspace.
+ * sm_guided_volume_i32: the same on one host frame, synchronous, through the handle's volume workspace. */
+SM_API int sm_guided_volume_device(sm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int width, int height,
+                                   int pitch, int radius, int num_disp, int32_t *d_vol, void *stream);
+SM_API int sm_guided_volume_i32(sm_handle *h, const uint8_t *left, const uint8_t *right, int width, int height,
+                                int pitch, int radius, int num_disp, int32_t *vol_out);
+/* Bytes of the handle's volume workspace one SM_AGG_GUIDED frame of the sub-pixel calls takes (host-only; see
+ * "sub-pixel disparity" below): 4 * P * num_disp for the costs and 4 * P for the LR check's planes, each rounded up
+ * to 256.  width 1..4096, radius 0..7, num_disp 1..256. */
+SM_API int sm_guided_workspace_bytes(int width, int height, int num_disp, int radius, size_t *bytes);
+
 /* d-slice keys of BOTH views from one fused pass (multi-GPU d-slices with the LR check, SURVEY §8e "LR adds
  * a second packed reduction for the right view"): d_left_keys as sm_slice_keys_device (flags SM_AGG_BOX,
  * uint32) or sm_guided_slice_keys_device (SM_AGG_GUIDED, int32), and d_right_keys the right view's keys,
@@ -414,9 +437,24 @@ SM_API int sm_census_volume_u8(sm_handle *h, const uint8_t *left, const uint8_t 
  *   and the right map is not needed unless asked for.  The right map is never checked (as in the 8-bit calls).
  * The arithmetic is exact for V < 2^24 (the bound under which the 8-bit (V << 8 | d) key fits 32 bits).
  *
- * sm_match_subpix_device: flags SM_AGG_BOX or SM_AGG_SGM, optionally | SM_COST_CENSUS | SM_LR_CHECK; radius <= 7,
+ * SM_AGG_GUIDED (optionally | SM_LR_CHECK), on a handle with SM_PARAM_GUIDED_SUBPIX = 1 (with the parameter at 0, the
+ *   default, or a null handle, the flag is refused: SM_ERR_INVALID_ARG, "no cost volume", naming the parameter):
+ *   per frame the one-pass guided volume (sm_guided_volume_device's costs) as
+ *   uint32 V = trunc(q * 2^14) + 512 * 2^14 < 2^24, and the rule above on V; the parabola does not depend on the bias.
+ *   Pairs of the 8-bit guided call: left view d <= min(num_disp - 1, W - x); right view V_R(u, d) = V(u + d, d) over
+ *   u + d < W.  An entry with d > W - x holds the largest cost, 2^24 - 1: the right view's walk crosses such entries and
+ *   never prefers one to a pair that exists.  Threshold: the left view is invalid where q >= 50, V >= (50 + 512) * 2^14,
+ *   the 8-bit guided call's rule; the right view has none.  SM_PARAM_UNIQUENESS > 0 is refused (the ratio test has no
+ *   meaning on a cost that can be negative), as are SM_PAIRS_IN_VIEW, SM_PARAM_MIN_DISP > 0, SM_COST_CENSUS, SM_AGG_SGM,
+ *   SM_STAGED and SM_DEVICE_CU_GRID beside the flag: SM_ERR_INVALID_ARG with a message, before any device work.
+ *   SM_PARAM_SUBPIX_MEDIAN, the LR check, the speckle filter and the row fill follow as for the other aggregations.
+ *   d0 is the first minimum of the quantised costs; the 8-bit guided call decides on the fp32 q, so the two may differ
+ *   where two costs lie within one quantum.  Workspace: sm_guided_workspace_bytes of the volume workspace.
+ *
+ * sm_match_subpix_device: flags SM_AGG_BOX, SM_AGG_SGM or SM_AGG_GUIDED, optionally | SM_COST_CENSUS (not with
+ * SM_AGG_GUIDED) | SM_LR_CHECK; radius <= 7,
  * width <= 4096.  SM_MEDIAN (the flag is the 8-bit ctmf median; these calls take SM_PARAM_SUBPIX_MEDIAN, below),
- * SM_AGG_GUIDED, SM_STAGED and SM_DEVICE_CU_GRID (no cost volume to interpolate) return SM_ERR_INVALID_ARG before any
+ * SM_STAGED and SM_DEVICE_CU_GRID (no cost volume to interpolate) return SM_ERR_INVALID_ARG before any
  * device work.  d_disp16: [batch][height]
  * [out_pitch], out_pitch and out_frame_stride in uint16 elements; d_right16 / d_mask: dense [batch][height][width],
  * either may be NULL.  Frames of a batch run one after another through the handle's volume workspace:
