@@ -5,7 +5,10 @@
 //
 // Tile: 64 x 64 input pixels from (x0 - R, y0 - R) -> TOY x TOX outputs: 48 rows (three 16-row blocks; the
 // fourth would be an edge block and its best keys the registers the paired loop needs) and 64 - 2R columns in
-// NXB = 4 blocks (R = 7: 48 columns in 3).  Four waves split the tile's d range and walk it two disparities per pass:
+// NXB = 4 blocks (R = 7: 48 columns in 3).  A tile's d range is [d_lo, d_hi) cut on the right at W - x0 (no output of
+// the tile has a larger valid d) and on the left one disparity past max(x_max + R + 1, d_lo), x_max the tile's last
+// output column: from there on every window lies left of d, costs 0 and loses to that first one.  Four
+// waves split the tile's d range and walk it two disparities per pass:
 // one L read, two R reads, v_min3_u32 on the two keys of a pixel.  Each wave keeps its best keys for the whole
 // tile in registers (12 * NXB VGPRs) in the accumulator layout, folded once at the end through LDS.  Ranges of at
 // most 32 disparities at R <= 2 run the same loop with one d per pass on 64 - 2R rows (NP = 1, launch_rd).
@@ -312,13 +315,18 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) best[ob][xb][i] = kInfBits;
 
-        // disparities past W - x0 are invalid for every output of the tile (Device.cu:44's break)
-        const int d_end = min(d_hi, W - x0 + 1);
+        // disparities past W - x0 are invalid for every output of the tile (Device.cu:44's break).  At the left edge
+        // of the frame the range ends early as well (valid_mode 0 only, this file's scope): a staged
+        // column c < d has AD = 0, so from d = x + R + 1 on the whole window of output column x lies left of d and
+        // its key is (0 << 8) | d; in [d_lo, d_hi) the first such d, max(x + R + 1, d_lo), beats all later ones.
+        // Past that disparity of its last output column x_max no key of the tile changes: that one pass still runs
+        const int x_max = min(x0 + G::TOX, W) - 1;
+        const int d_end = min(min(d_hi, W - x0 + 1), max(x_max + R + 1, d_lo) + 1);
         const int nd = max(d_end - d_lo, 0);
         const int dw_lo = d_lo + (wave * nd) / kNW;
         const int dw_hi = d_lo + ((wave + 1) * nd) / kNW;
         // largest d valid for every output of the tile
-        const int d_free = W - (min(x0 + G::TOX, W) - 1);
+        const int d_free = W - x_max;
         // Both masks are monotone in d: a staged column c needs AD = 0 where c < d (from d = x0 - R + 1 on) or c >= W
         // (every d), an output column x has no key where d > W - x (from d = d_free + 1 on).  d_m is the first
         // disparity of the tile that needs either; each wave walks the whole passes below it in the unmasked loop and
@@ -513,7 +521,8 @@ __device__ __forceinline__ void box_mfma_tiles(const MatchArgs& a, int tiles_x, 
             //   rcol    byte offset of p = 0's column l16 + DMAX + d_lo - d, - 2 columns per pass.  slot()'s swizzle
             //           (col >> 1) & 7 is bits 8..10 of it, so an address is a shift, an and-xor and an add
             //   raddr[] the two R addresses of the pass; p = 1 reads one column to the left, or p = 0's in an odd
-            //           last pass (dd[] decides, as it does in run())
+            //           last pass (dd[] decides, as it does in run()).  The clamp is against the wave's own hi, at most
+            //           the tile's d_end <= d_lo + DMAX, so every staged column read lies in [0, RC)
             // The addresses are LDS addresses, not offsets into smem[] to which every read adds the array's own
             // address again: smem is aligned to a whole swizzle period, so the swizzle of an address is the swizzle
             // of the offset
